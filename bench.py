@@ -2,13 +2,15 @@
 """Headline benchmark: CADDY full-model training step (E -> A -> R -> D forward, fused losses, BPTT backward, gradient
 all-reduce for N>1, Adam) on synthetic BAIR-shaped clips -- BASELINE.json configs[1]: 256x256, T=16, B=8 per GPU.
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  `value` = clips/s over all GPUs with inputs resident in HBM (observations never cross PCIe inside
 the step).  The step is the reference's real one: forward_full_model + L1 / VGG19-perceptual / states / KL / MI losses + BPTT + Adam.
-Two legs are timed in one run: the full step (`value`, `ms_per_step`; VGG19 perceptual term inside) and `erad_only` -- the same step with the
-perceptual term switched off, i.e. exactly the E -> R -> A -> D forward + backward the north star's roofline target is quoted on.
+A plain run sets up, warms up, times `--steps` full steps (`value`, `ms_per_step`; VGG19 perceptual term inside), writes the last timed step's
+results with `--dump-outputs DIR` and prints the line.  Everything below is measured only with `--full`:
+`erad_only` -- the same step with the perceptual term switched off, i.e. exactly the E -> R -> A -> D forward + backward the north star's
+roofline target is quoted on.
 `roofline` is for the dominant kernel of the E/R/A/D leg (`k_conv_hx`: 3x3 convolutions on the 16-bit matrix pipe with split fp32
 operands), timed with HIP events on the launch stream during extra profiled steps, plus `erad_hbm_frac` = SURVEY 8(d)'s 55.2 GB / t_erad /
 8 TB/s; the dominant kernel of the full step (a VGG19 layer) is kept as `roofline_full_step`.  `exact_fp32_ms_per_step` is the same step on the
@@ -223,8 +225,12 @@ def main():
     ap.add_argument("--no-plugin", action="store_true", help="skip the leg that times the plugin path (model / trainer factories + train_epoch)")
     ap.add_argument("--no-extra-legs", action="store_true", help="only the contract's timed region (+ profiled steps): no erad_only / exact-fp32 / plugin legs")
     ap.add_argument("--quick", action="store_true", help="A/B aid: the timed region + the erad_only leg; no exact-fp32 / deterministic / plugin / roll-out legs")
+    ap.add_argument("--full", action="store_true", help="also the legs beyond the headline figure: erad_only, profiled roofline steps, exact-fp32 and atomic "
+                                                        "backward, roll-out, plugin path, CPU baseline (each can still be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps: write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     a = ap.parse_args()
     if a.quick:
+        a.full = True
         a.no_plugin = a.no_rollout = True
 
     if not torch.cuda.is_available():
@@ -275,6 +281,34 @@ def roofline_of(fam, recs, nsteps, pm, pm_file, note):
     return roof
 
 
+DUMP_SAMPLE = 1 << 20            # elements kept of each large optimiser-side tensor (a fixed, seeded sample)
+DUMP_PARAMS_MAX = 12 << 20       # parameters are written whole up to this many floats (BAIR main: 9.9 M)
+
+
+def dump_outputs(out_dir, eng, losses):
+    """What the timed path hands its caller after the last timed step, as <name>.npy (float64 scalars, float32 tensors; < 64 MB in all):
+    every loss value, the updated parameters (+ BatchNorm buffers), the MI estimator matrix, and the same fixed seeded sample of the
+    gradients and of both Adam moments.  The inputs are seeded, so two builds can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(t, n):
+        if t.numel() <= n:
+            return t
+        idx = torch.randint(t.numel(), (n,), generator=torch.Generator().manual_seed(0)).sort().values
+        return t[idx.to(t.device)]
+
+    arrays = {f"loss_{k}": np.float64(v) for k, v in losses.items() if isinstance(v, (int, float))}
+    arrays["params"] = sample(eng.params, DUMP_PARAMS_MAX)
+    if eng.mi_ema is not None:
+        arrays["mi_ema"] = eng.mi_ema
+    for name, t in (("grads_sample", eng.grads), ("adam_m_sample", eng.adam_m), ("adam_v_sample", eng.adam_v)):
+        if t is not None:
+            arrays[name] = sample(t, DUMP_SAMPLE)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, np.float64))
+
+
 def run(a, dev, lib=None, backend="nccl"):
     """The benchmark proper.  `lib` / `backend` exist so that tests/test_cabi_and_dp.py can drive the multi-rank control flow
     (hooks, collectives, profiled steps on every rank, max-over-ranks timing) on CPU with gloo and the simulator build."""
@@ -293,7 +327,8 @@ def run(a, dev, lib=None, backend="nccl"):
     B, T, H, W, S, K, Da = wl["batch"], wl["seq_len"], wl["height"], wl["width"], wl["stacking"], wl["actions"], wl["action_dim"]
     too_small = H < 64 or W < 64                           # the quarter-resolution image must survive VGG19's four max-pools
     perc = not getattr(a, "no_perceptual", False) and not too_small
-    extra = not getattr(a, "no_extra_legs", False)
+    full = getattr(a, "full", False)                      # plain run: set-up, warm-up, the timed steps, the outputs, the line -- nothing else
+    extra = full and not getattr(a, "no_extra_legs", False)
     eng = Engine(variant=wl["variant"], batch=B, seq_len=T, height=H, width=W, stacking=S, actions=K, action_dim=Da, hidden=wl["hidden"], device=dev, lib=lib,
                  perceptual=perc)
     log(f"engine created: workspace {eng.ws_bytes / 2**30:.1f} GiB, {eng.n_train} trainable floats")
@@ -355,6 +390,9 @@ def run(a, dev, lib=None, backend="nccl"):
         log(f"warm-up step {i} done, loss {losses['total']:.5f}")
     ms_step, losses = timed(a.steps)                        # ---- the contract's timed region: EXACTLY K steps of the full step ----
     log(f"timed region done: {ms_step:.1f} ms/step")
+    if rank == 0 and getattr(a, "dump_outputs", None):
+        dump_outputs(a.dump_outputs, eng, losses)
+        log(f"outputs of the last timed step written to {a.dump_outputs}")
     clips_s = world * B * 1e3 / ms_step
 
     # ---- E -> R -> A -> D leg: the same step without the VGG19 term (weight 0 and no ground-truth VGG19 branch beside the forward) ----
@@ -367,7 +405,7 @@ def run(a, dev, lib=None, backend="nccl"):
 
     # ---- live per-kernel timing (HIP events on the launch stream) of extra, untimed-for-throughput steps: E/R/A/D leg first, then the full step ----
     roof = roof_full = None
-    nprof = a.profile_steps
+    nprof = a.profile_steps if full else 0
     legs = [("erad", loss_w_erad)] + ([("full", loss_w)] if perc else [])
     for leg, weights in legs if nprof > 0 else []:
         if leg == "full":
@@ -456,17 +494,18 @@ def run(a, dev, lib=None, backend="nccl"):
                                   + (" (VGG19: random-init weights)" if perc else
                                      (" (VGG19 perceptual term not applicable: frames below 64x64)" if too_small else " (VGG19 perceptual term DISABLED by --no-perceptual)"))},
                "loss": losses["total"], "rccl_ranks_seen": ranks_seen, "dp_native": dp_native,
-               "erad_only": {"ms_per_step": ms_erad, "clips_per_s": world * B * 1e3 / ms_erad, "what": "the same step with perceptual weight 0 and no VGG19 branch: E -> R -> A -> D forward + L1 / states / KL / MI losses + BPTT + Adam"},
-               "exact_fp32_ms_per_step": ms_exact,
-               "backward": "bit-reproducible (library default since round 5: slabs + fixed-order folds; two backward passes over one forward give bit-identical gradients)",
-               "atomic_backward": {"ms_per_step": ms_det, "erad_only_ms_per_step": ms_det_erad,
-                                   "what": "caddy_set_deterministic(0): fp32 atomics in arrival order instead of slabs + fixed-order folds -- the non-reproducible form, for comparison"},
-               "roofline": roof, "roofline_full_step": roof_full}
+               "backward": "bit-reproducible (library default since round 5: slabs + fixed-order folds; two backward passes over one forward give bit-identical gradients)"}
+        if full:
+            res.update({"erad_only": {"ms_per_step": ms_erad, "clips_per_s": world * B * 1e3 / ms_erad, "what": "the same step with perceptual weight 0 and no VGG19 branch: E -> R -> A -> D forward + L1 / states / KL / MI losses + BPTT + Adam"},
+                        "exact_fp32_ms_per_step": ms_exact,
+                        "atomic_backward": {"ms_per_step": ms_det, "erad_only_ms_per_step": ms_det_erad,
+                                            "what": "caddy_set_deterministic(0): fp32 atomics in arrival order instead of slabs + fixed-order folds -- the non-reproducible form, for comparison"},
+                        "roofline": roof, "roofline_full_step": roof_full})
     del eng
     if on_gpu:
         torch.cuda.empty_cache()
     if rank == 0:
-        if world == 1 and not a.no_rollout and on_gpu:
+        if world == 1 and full and not a.no_rollout and on_gpu:
             res["rollout"] = rollout_fps(dev)
             log(f"roll-out: {res['rollout']['value']:.1f} frames/s")
         if world == 1 and extra and not getattr(a, "no_plugin", False) and on_gpu:
@@ -475,7 +514,7 @@ def run(a, dev, lib=None, backend="nccl"):
             res["plugin"] = plugin_leg(wl, dev, max(a.steps, 12), a.warmup, perc)      # (>= 12 steps: an epoch's fixed costs -- first un-overlapped H2D copy, the last deferred loss read -- are not per-step costs)
             res["plugin"]["vs_engine_step"] = res["plugin"]["ms_per_step"] / ms_step
             log(f"plugin path: {res['plugin']['ms_per_step']:.1f} ms/step ({res['plugin']['vs_engine_step']:.3f} x the engine-level step)")
-        if world == 1 and not a.no_cpu_baseline and on_gpu:
+        if world == 1 and full and not a.no_cpu_baseline and on_gpu:
             log("cpu baseline (oracle, 1 clip) ...")
             res["cpu_baseline"] = cpu_baseline(wl, perceptual=perc)
             log("cpu baseline done")

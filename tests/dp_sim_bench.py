@@ -26,7 +26,7 @@ def main():
     torch.set_num_threads(1)
     dist.init_process_group("gloo")      # RANK / WORLD_SIZE / MASTER_* from the launcher, as on the GPU node
     configs.WORKLOADS["tiny"] = dict(configs.BREAKOUT, batch=1, seq_len=3, height=32, width=32, gt_init=2, tau=0.8)
-    ns = argparse.Namespace(gpus=a.gpus, steps=a.steps, warmup=a.warmup, workload="tiny", no_cpu_baseline=True, profile_steps=1, no_rollout=True)
+    ns = argparse.Namespace(gpus=a.gpus, steps=a.steps, warmup=a.warmup, workload="tiny", no_cpu_baseline=True, profile_steps=1, no_rollout=True, full=True)
     res = bench.run(ns, torch.device("cpu"), lib=load_emu(), backend="gloo")
     if int(os.environ.get("RANK", "0")) == 0:
         out = os.environ.get("CADDY_DP_SIM_OUT")

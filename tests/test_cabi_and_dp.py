@@ -145,7 +145,7 @@ def _bench_worker(rank, world, port, out):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     import bench
     configs.WORKLOADS["tiny"] = dict(configs.BREAKOUT, batch=1, seq_len=3, height=32, width=32, gt_init=2, tau=0.8)
-    a = argparse.Namespace(gpus=world, steps=2, warmup=1, workload="tiny", no_cpu_baseline=True, profile_steps=1, no_rollout=True)
+    a = argparse.Namespace(gpus=world, steps=2, warmup=1, workload="tiny", no_cpu_baseline=True, profile_steps=1, no_rollout=True, full=True)
     res = bench.run(a, torch.device("cpu"), lib=load_emu(), backend="gloo")
     if rank == 0:
         with open(os.path.join(out, "bench.json"), "w") as f:
@@ -188,6 +188,59 @@ def test_bench_world8_through_the_launch_script_on_the_simulator(tmp_path):
     assert res["n_gpus"] == 8 and res["rccl_ranks_seen"] == 8 and res["config"]["global_batch"] == 8 and res["config"]["parallelism"] == "dp8"
     assert res["scaling"] == "weak" and res["value"] > 0 and res["steps"] == 2 and res["warmup"] == 1 and res["roofline"] is not None
     assert res["value"] == pytest.approx(8 * 1 * 1e3 / res["ms_per_step"])      # whole-job clips/s over all ranks
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path, monkeypatch):
+    """bench.run() without --full on the simulator: the headline keys and nothing of the extra legs; --dump-outputs writes the last timed step's
+    losses / parameters / optimiser samples as float32 / float64 .npy (< 64 MB), identical from run to run with the same arguments."""
+    import argparse
+    import numpy as np
+    from tests.emu.loader import load_emu
+    from playablevideogeneration_amd import configs
+    import bench
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setitem(configs.WORKLOADS, "tiny", dict(configs.BREAKOUT, batch=1, seq_len=3, height=32, width=32, gt_init=2, tau=0.8))
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        a = argparse.Namespace(gpus=1, steps=2, warmup=1, workload="tiny", dump_outputs=str(out))
+        res = bench.run(a, torch.device("cpu"), lib=load_emu(), backend="gloo")
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in res
+        assert res["steps"] == 2 and res["value"] == pytest.approx(1e3 / res["ms_per_step"])
+        assert not {"erad_only", "roofline", "rollout", "plugin", "cpu_baseline"} & set(res)
+        files = {f.name: np.load(f) for f in sorted(out.glob("*.npy"))}
+        assert {"loss_total.npy", "params.npy", "mi_ema.npy", "grads_sample.npy", "adam_m_sample.npy", "adam_v_sample.npy"} <= set(files)
+        assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+        assert sum(f.stat().st_size for f in out.glob("*.npy")) <= 64 << 20
+        assert float(files["loss_total.npy"]) == res["loss"]
+        dumps.append(files)
+    for name, v in dumps[0].items():
+        assert np.array_equal(v, dumps[1][name]), name
+    # the dump is the state after warm-up + timed steps: replay the same seeded steps on a fresh engine and compare
+    from playablevideogeneration_amd.engine import Engine
+    from playablevideogeneration_amd.init import init_parameters
+    wl, dev = configs.WORKLOADS["tiny"], torch.device("cpu")
+    B, T, K, Da = wl["batch"], wl["seq_len"], wl["actions"], wl["action_dim"]
+    eng = Engine(variant=wl["variant"], batch=B, seq_len=T, height=wl["height"], width=wl["width"], stacking=wl["stacking"], actions=K, action_dim=Da,
+                 hidden=wl["hidden"], device=dev, lib=load_emu(), perceptual=False)
+    init_parameters(eng, seed=0)
+    init = eng.params.clone()
+    gen = torch.Generator(device=dev).manual_seed(1234)
+    obs = torch.rand(B, T, 3 * wl["stacking"], wl["height"], wl["width"], device=dev, generator=gen) * 2 - 1
+    for i in range(3):                                            # 1 warm-up + 2 timed steps
+        eng.forward_full(obs, wl["gt_init"], wl["tau"], bench.make_noise(B, T, K, Da, dev, gen), training=True, fetch_outputs=False)
+        losses = eng.loss_backward(dict(configs.LOSS_WEIGHTS, perceptual=0.0), smooth_mi=True)
+        eng.adam_step(i + 1, lr=4e-4, weight_decay=1e-6, grad_scale=1.0)
+    d = dumps[0]
+    assert float(d["loss_total.npy"]) == losses["total"]
+    assert np.array_equal(d["params.npy"], eng.params.numpy()) and not np.array_equal(d["params.npy"], init.numpy())
+    assert np.array_equal(d["mi_ema.npy"], eng.mi_ema.numpy())
+    idx = torch.randint(eng.grads.numel(), (d["grads_sample.npy"].size,), generator=torch.Generator().manual_seed(0)).sort().values
+    for name, t in (("grads_sample.npy", eng.grads), ("adam_m_sample.npy", eng.adam_m), ("adam_v_sample.npy", eng.adam_v)):
+        assert np.array_equal(d[name], t[idx].numpy()), name
+    assert (d["adam_v_sample.npy"] > 0).mean() > 0.5 and np.abs(d["grads_sample.npy"]).max() > 0
 
 
 def _trainer_worker(rank, world, port, out, skew=0.0, ens=1):

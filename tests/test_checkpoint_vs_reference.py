@@ -1,20 +1,17 @@
-"""Checkpoint interchange with the REAL reference trainer (build container only: needs /root/reference; skipped elsewhere).
-A checkpoint written by training/smooth_mi_trainer.py resumes in the trainer mirror and vice versa: after loading, one more training step
-on the same seeded batch must give the same weights on both sides (model state, Adam moments + step count, LR schedule, MI estimator)."""
+"""Checkpoint interchange with the REAL reference trainer, through what it stored (tools/gen_checkpoint_golden.py; tests/golden/ckpt_mirror_to_reference.npz):
+a checkpoint written by the trainer mirror has the layout of the one training/smooth_mi_trainer.py writes, and after the reference loaded it, one more
+training step on the same seeded batch gave the weights the mirror reaches (model state, Adam moments + step count, LR schedule, MI estimator)."""
 import os
-import random
-import sys
-import types
 
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
 from oracle import caddy_oracle as O
+from tests.helpers import GOLDEN
 from tests.test_host_api_emu import PRE_W, _config, _make_model
 
-pytestmark = [pytest.mark.emu, pytest.mark.skipif(not os.path.isdir("/root/reference/model"), reason="reference tree only exists in the build container")]
+pytestmark = [pytest.mark.emu]
 
 
 def _cfg(tmp):
@@ -28,28 +25,20 @@ def _cfg(tmp):
     return cfg
 
 
-def _reference_side(cfg, P):
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import ref_harness as rh
-    rh.install()
-    rcfg = dict(cfg, model=dict(cfg["model"], architecture="model.reduced_model.model"))
-    rcfg["model"]["action_network"] = dict(cfg["model"]["action_network"], use_variations=True)
-    ref = nn.DataParallel(rh.build_reference_model(rcfg, P))
-    import training.smooth_mi_trainer as SM
-    logger = types.SimpleNamespace(print=lambda *a, **k: None, get_wandb=lambda: types.SimpleNamespace(log=lambda *a, **k: None))
-    tr = SM.SmoothMITrainer(rcfg, ref, [0] * 8, logger)
-    ref.train()
-    return ref, tr
+def _inputs(cfg):
+    d = O.Dims.from_config(dict(cfg, model=dict(cfg["model"], architecture="model.reduced_model.model")))
+    obs = torch.rand(2, 3, 3, 64, 64, generator=torch.Generator().manual_seed(1)) * 2 - 1      # small clip; 64x64 is the smallest frame the reference trainer's VGG19 accepts
+    return O.make_params(d, seed=7), obs
 
 
-def _ref_step(ref, tr, obs, seed):
-    acts = torch.zeros(obs.shape[0], obs.shape[1], dtype=torch.int32)
-    batch = types.SimpleNamespace(observations=obs, actions=acts, size=obs.shape[1], to_tuple=lambda cuda=True: (obs, acts, None, None))
-    torch.manual_seed(seed); random.seed(seed)
-    tr.global_step += 1
-    loss, info, _ = tr.compute_losses(ref, batch, obs.shape[1])
-    tr.optimizer.zero_grad(); loss.backward(); tr.optimizer.step(); tr.lr_scheduler.step()
-    return loss.item()
+def _mirror_side(cfg, P):
+    from playablevideogeneration_amd import smooth_mi_trainer
+    m = _make_model(cfg)
+    m.load_state_dict(P)
+    m.train()
+    mtr = smooth_mi_trainer.trainer(cfg, m, dataset=None, logger=None)
+    mtr.global_step = 5000
+    return m, mtr
 
 
 def _mirror_step(m, tr, obs, seed):
@@ -61,39 +50,39 @@ def _mirror_step(m, tr, obs, seed):
 
 
 def _close(m, ref, lr):
-    """weights equal up to a few elements per tensor whose ~0 gradient moved the other way (Adam: 2 * lr per such element)"""
+    """weights equal up to a few elements per tensor whose ~0 gradient moved the other way (Adam: 2 * lr per such element), on the stored sample"""
     sd = dict(m.named_parameters())
-    for n, p in ref.module.named_parameters():
-        a, b = sd[n].detach().double(), p.detach().double()
+    names = [k[len("param."):] for k in ref.files if k.startswith("param.")]
+    assert set(names) == set(sd)
+    for n in names:
+        a, b = sd[n].detach().reshape(-1)[torch.from_numpy(ref["idx." + n])].double(), torch.from_numpy(ref["param." + n]).double()
         assert (a - b).abs().max().item() <= 2.5 * lr + 1e-6, (n, (a - b).abs().max().item())
         # elements whose gradient is pure round-off (|g| ~ 1e-12) take +-lr steps at random in BOTH implementations: allow 3 % of a tensor
         assert ((a - b).abs() > 1e-5).sum().item() <= max(4, 0.03 * a.numel()), (n, ((a - b).abs() > 1e-5).sum().item(), a.numel())
 
 
-@pytest.mark.parametrize("direction", ["reference_to_mirror", "mirror_to_reference"])
+def _layout(st):
+    """what a loader relies on in a checkpoint: entries, model tensor names / shapes, parameters per optimizer group and their Adam state,
+    public scheduler entries (torch adds private ones from version to version) and estimator entries"""
+    opt = st["optimizer"]
+    return {"keys": sorted(st), "model": sorted((k, tuple(v.shape)) for k, v in st["model"].items()),
+            "param_groups": [len(g["params"]) for g in opt["param_groups"]],
+            "state": sorted((tuple(sorted(v)), tuple(v["exp_avg"].shape)) for v in opt["state"].values()),
+            "lr_scheduler": sorted(k for k in st["lr_scheduler"] if not k.startswith("_")), "mi_estimator": sorted((k, tuple(v.shape)) for k, v in st["mi_estimator"].items())}
+
+
+@pytest.mark.parametrize("direction", ["mirror_to_reference"])
 def test_checkpoint_interchange(tmp_path, direction):
-    from playablevideogeneration_amd import smooth_mi_trainer
     cfg = _cfg(tmp_path)
-    d = O.Dims.from_config(dict(cfg, model=dict(cfg["model"], architecture="model.reduced_model.model")))
-    P = O.make_params(d, seed=7)
-    obs = torch.rand(2, 3, 3, 64, 64, generator=torch.Generator().manual_seed(1)) * 2 - 1      # small clip; 64x64 is the smallest frame the reference trainer's VGG19 accepts
-    ref, rtr = _reference_side(cfg, P)
-    m = _make_model(cfg)
-    m.load_state_dict(P)
-    m.train()
-    mtr = smooth_mi_trainer.trainer(cfg, m, dataset=None, logger=None)
-    rtr.global_step = mtr.global_step = 5000
-    if direction == "reference_to_mirror":
-        _ref_step(ref, rtr, obs, 20)
-        rtr.save_checkpoint(ref)                                   # <root>/latest.pth.tar, written by the REAL reference
-        mtr.load_checkpoint(m)
-        assert mtr.global_step == rtr.global_step and mtr.opt_steps == 1
-        assert np.allclose(mtr.mi_ema.numpy(), rtr.mutual_information_loss.matrix_estimator.estimated_matrix.detach().numpy(), atol=1e-7)
-    else:
-        _mirror_step(m, mtr, obs, 20)
-        mtr.save_checkpoint(m)
-        rtr.load_checkpoint(ref.module)                            # the REAL reference loads the mirror's file (model, optimizer, lr_scheduler, mi_estimator, step); unwrapped module: its state_dict keys carry no "module." prefix
-        assert rtr.global_step == mtr.global_step
-    la, lb = _ref_step(ref, rtr, obs, 31), _mirror_step(m, mtr, obs, 31)
+    P, obs = _inputs(cfg)
+    m, mtr = _mirror_side(cfg, P)
+    ref = np.load(os.path.join(GOLDEN, "ckpt_mirror_to_reference.npz"))      # the REAL reference's step after loading the mirror's checkpoint
+    _mirror_step(m, mtr, obs, 20)
+    mtr.save_checkpoint(m)
+    mine = _layout(torch.load(tmp_path / "latest.pth.tar", map_location="cpu", weights_only=True))
+    assert repr(mine) == str(ref["reference_layout"])                       # the layout of the reference's own latest.pth.tar
+    assert mtr.global_step == int(ref["global_step"]) - 1
+    la, lb = float(ref["loss"]), _mirror_step(m, mtr, obs, 31)
     assert abs(la - lb) < 5e-5 * max(1.0, abs(la)), (la, lb)
+    assert np.allclose(mtr.mi_ema.numpy(), ref["mi_ema"], atol=1e-6)
     _close(m, ref, 4e-4)

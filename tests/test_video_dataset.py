@@ -1,7 +1,6 @@
 """Input-pipeline mirror: `playablevideogeneration_amd.video_dataset` reads the reference's on-disk video format and
-produces the same BatchElements as the reference's `dataset.video_dataset.VideoDataset` (compared directly when /root/reference is present)."""
+produces the same BatchElements as the reference's `dataset.video_dataset.VideoDataset` (compared with its stored output, tests/golden/video_dataset_ref.npz)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -11,7 +10,6 @@ from playablevideogeneration_amd import batching as BT
 from playablevideogeneration_amd import video_dataset as VD
 from playablevideogeneration_amd.evaluation_dataset_builder import EvaluationVideo
 
-REF = os.environ.get("CADDY_REFERENCE", "/root/reference")
 H, W = 20, 24
 
 
@@ -90,35 +88,29 @@ def test_crop_resize_transform_and_splits(tmp_path):
         VD.generate_splits(dict(cfg, data=dict(cfg["data"], dataset_style="other")))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout (build container only)")
-def test_against_the_reference_dataset_classes(tmp_path):
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import ref_harness
-    ref_harness.install()
-    from dataset.video_dataset import VideoDataset as RefDataset
-    from dataset.dataset_splitter import DatasetSplitter
-    from dataset.batching import single_batch_elements_collate_fn as ref_collate
+def test_against_the_reference_dataset_classes_golden(tmp_path):
+    """the reference's VideoDataset / single_batch_elements_collate_fn / DatasetSplitter on the same seeded dataset, stored by
+    tools/gen_dataset_golden.py (tests/golden/video_dataset_ref.npz): every element, the collate and the splits are equal"""
+    import ast
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "video_dataset_ref.npz"))
     root = str(tmp_path / "ds")
     os.makedirs(root)
     _write_dataset(root, seed=5)
     cfg = _config(root, [1, 2, 21, 18], (12, 10))
     tf = VD.final_transform(cfg)
     for key in ("training", "evaluation"):
-        bc = cfg[key]["batching"]
-        mine, ref = VD.VideoDataset(root, bc, tf), RefDataset(root, bc, tf)
-        assert len(mine) == len(ref)
-        for i in range(len(ref)):
-            a, b = mine[i], ref[i]
-            assert a.actions == b.actions and a.rewards == b.rewards and a.dones == b.dones and a.initial_frame_index == b.initial_frame_index
-            for sa, sb in zip(a.observations, b.observations):
-                for fa, fb in zip(sa, sb):
-                    assert torch.equal(fa, fb)
-        ba, bb = BT.single_batch_elements_collate_fn([mine[0], mine[2]]), ref_collate([ref[0], ref[2]])
-        for x, y in zip(ba.to_tuple(cuda=False), bb.to_tuple(cuda=False)):
-            assert torch.equal(x, y)
-    rs = DatasetSplitter.generate_splits(cfg)
+        mine = VD.VideoDataset(root, cfg[key]["batching"], tf)
+        assert len(mine) == int(z[f"{key}_len"])
+        for i in range(len(mine)):
+            a = mine[i]
+            assert a.actions == z[f"{key}_{i}_actions"].tolist() and a.rewards == z[f"{key}_{i}_rewards"].tolist()
+            assert a.dones == z[f"{key}_{i}_dones"].tolist() and a.initial_frame_index == int(z[f"{key}_{i}_initial_frame_index"])
+            assert torch.equal(torch.stack([torch.stack(list(s)) for s in a.observations]), torch.from_numpy(z[f"{key}_{i}_observations"]))
+        for j, x in enumerate(BT.single_batch_elements_collate_fn([mine[0], mine[2]]).to_tuple(cuda=False)):
+            assert torch.equal(x, torch.from_numpy(z[f"{key}_collate_{j}"])), (key, j)
     ms = VD.generate_splits(cfg)
-    assert {k: (v[0], v[2]) for k, v in rs.items()} == {k: (v[0], v[2]) for k, v in ms.items()}
+    assert {k: v[0] for k, v in ms.items()} == {k: root for k in ms}
+    assert {k: v[2] for k, v in ms.items()} == ast.literal_eval(str(z["splits"]))
 
 
 def test_mse_psnr_metrics():
@@ -130,7 +122,5 @@ def test_mse_psnr_metrics():
     p = MT.psnr(a * 255, b * 255, 255.0)
     assert torch.allclose(p, -10 * torch.log10(m + 1e-8), atol=1e-4)
     assert abs(MT.psnr(a, a)[0, 0].item() - 80.0) < 1e-3                         # the stabilising constant caps identical frames at 80 dB
-    if os.path.isdir(REF):
-        sys.path.insert(0, REF)
-        from evaluation.metrics.psnr import PSNR
-        assert torch.allclose(PSNR()(a, b), MT.psnr(a, b), atol=1e-6)
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "video_dataset_ref.npz"))["psnr"]      # the reference's PSNR (tools/gen_dataset_golden.py)
+    assert torch.allclose(torch.from_numpy(ref), MT.psnr(a, b), atol=1e-6)
