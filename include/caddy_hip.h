@@ -125,6 +125,21 @@ int caddy_perceptual_per_frame(caddy_ctx* ctx, double* out_host);
  * either may be NULL; waits for the stream. */
 int caddy_sequence_losses_per_frame(caddy_ctx* ctx, double* l1_host, double* mse_host);
 int caddy_set_vgg_precision(caddy_ctx* ctx, int forward, int dgrad);
+/* --- Dataset evaluation: replaces the frame-quality metrics of evaluation/dataset_evaluator.py:150-170 -- MSE (evaluation/metrics/mse.py), MotionMaskedMSE
+ *     (evaluation/metrics/motion_masked_mse.py + motion_mask.py), PSNR (evaluation/metrics/psnr.py), SSIM (evaluation/metrics/ssim.py: piq.ssim), VGGCosineSimilarity
+ *     (evaluation/metrics/vgg_cosine_similarity.py) and the inputs of DatasetEvaluator.check_range.  A METRICS context holds no model: frames of height x width, the fused
+ *     pass in chunks of max_frames frames; vgg != 0 adds the VGG19 feature network (weights through caddy_load_vgg, arithmetic through caddy_set_vgg_precision).
+ *     caddy_metrics_workspace_bytes returns 0 (caddy_last_error) for frames smaller than SSIM's 11 x 11 window after its down-sampling, or, with vgg, sides that are not
+ *     multiples of 16.  Destroy with caddy_ctx_destroy. --- */
+size_t caddy_metrics_workspace_bytes(int max_frames, int height, int width, int vgg);
+caddy_ctx* caddy_metrics_ctx_create(int max_frames, int height, int width, int vgg, void* workspace, size_t bytes);
+/* ref / gen: (B, T, 3, height, width) fp32 device tensors (the reference's (bs, observations_count, channels, height, width)); frame n = b * T + t.  out_host (host memory,
+ * CADDY_FM_COUNT * B * T doubles): out_host[slot * N + n], N = B * T.  MSE and the motion-masked MSE on the raw values (the motion mask from the REFERENCE frames, 0 at t = 0),
+ * PSNR = -10 log10(MSE / range^2 + 1e-8), SSIM of gen / range against ref / range, the VGG19 cosine similarity (mean over relu1_1 .. relu5_1; want_vgg != 0, else NaN) and the
+ * per-frame minima / maxima of ref and gen (check_range).  Deterministic: two calls on the same input give bit-identical results.  Waits for the stream. */
+int caddy_frame_metrics(caddy_ctx* ctx, const float* ref, const float* gen, int B, int T, float value_range, int want_vgg, double* out_host);
+enum { CADDY_FM_MSE, CADDY_FM_MOTION_MSE, CADDY_FM_PSNR, CADDY_FM_SSIM, CADDY_FM_VGG_SIM,
+       CADDY_FM_REF_MIN, CADDY_FM_REF_MAX, CADDY_FM_GEN_MIN, CADDY_FM_GEN_MAX, CADDY_FM_COUNT };
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

@@ -236,6 +236,10 @@ struct caddy_ctx {
     bool seeds_only = false;         // caddy_debug_set_seeds_only: caddy_loss_backward stops after the loss kernels (tests of the loss gradient seeds)
     bool poison_nz = false;          // caddy_debug_set_poison: NaN-fill the first-touch gradient region before every backward (tests)
     int hs, ws;   // state resolution
+    // dataset evaluation (caddy_metrics_ctx_create): a context without a model -- the fused frame-metric pass (frame_metrics.hip) and, with VGG19 weights, the cosine similarity
+    bool metrics_only = false;
+    double* fm_slab = nullptr;       // per (frame, tile) partials of the fused pass (cfg.batch = max_frames frames)
+    double* fm_out = nullptr;        // CADDY_FM_COUNT x max_frames results of the current chunk
 
     // ---- optional per-launch timing of the conv kernels (HIP events on the launch stream; bench.py roofline) ----
     struct ProfRec { hipEvent_t a, b; int fam; double flops; int P, K, Cout, KS, kind; double bytes; };   // kind: 0 fwd, 1 dgrad (accumulate), 2 wgrad

@@ -136,6 +136,48 @@ __global__ __launch_bounds__(256) void k_feat_l1_img(const float* rec, const flo
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(acc + blockIdx.y, sh[0] + sh[1] + sh[2] + sh[3]);
 }
+// per IMAGE and block: the partials x.y, |x|^2, |y|^2 of image n's feature maps (blockIdx.y = image), written to part[(n * gridDim.x + blockIdx.x) * 3 + {0, 1, 2}] --
+// no atomics, a fixed reduction order (the dataset evaluation's VGG cosine similarity, evaluation/metrics/vgg_cosine_similarity.py:47-55; finalised by k_feat_cos_finalize)
+template <bool RS, bool GS>
+__global__ __launch_bounds__(256) void k_feat_cos_img(const float* x, const float* y, long n4_img, double* part) {
+    __shared__ double sh[4][3];
+    const float* x4 = x + 4 * (long)blockIdx.y * n4_img;
+    const float* y4 = y + 4 * (long)blockIdx.y * n4_img;
+    double sxy = 0.0, sxx = 0.0, syy = 0.0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4_img; i += (long)gridDim.x * 256) {
+        const float4 a = ld4<RS>(x4, i), b = ld4<GS>(y4, i);
+        sxy += (double)a.x * b.x + (double)a.y * b.y + (double)a.z * b.z + (double)a.w * b.w;
+        sxx += (double)a.x * a.x + (double)a.y * a.y + (double)a.z * a.z + (double)a.w * a.w;
+        syy += (double)b.x * b.x + (double)b.y * b.y + (double)b.z * b.z + (double)b.w * b.w;
+    }
+    for (int o = 32; o > 0; o >>= 1) { sxy += __shfl_xor(sxy, o); sxx += __shfl_xor(sxx, o); syy += __shfl_xor(syy, o); }
+    if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6][0] = sxy; sh[threadIdx.x >> 6][1] = sxx; sh[threadIdx.x >> 6][2] = syy; }
+    __syncthreads();
+    if (threadIdx.x < 3) part[((long)blockIdx.y * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+struct CosLevels { long off[5]; int blocks[5]; };      // part region and blocks per image of each feature level
+// one thread per image: the blocks of each level in order -> cosine x.y / (max(|x|, 1e-6) max(|y|, 1e-6)) (F.cosine_similarity(dim=1, eps=1e-6)), mean over the 5 levels
+__global__ __launch_bounds__(64) void k_feat_cos_finalize(const double* part, CosLevels lv, int nf, double* out) {
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= nf) return;
+    double sim = 0.0;
+    for (int l = 0; l < 5; l++) {
+        const double* p = part + lv.off[l] + (long)n * lv.blocks[l] * 3;
+        double sxy = 0.0, sxx = 0.0, syy = 0.0;
+        for (int k = 0; k < lv.blocks[l]; k++) { sxy += p[3 * k]; sxx += p[3 * k + 1]; syy += p[3 * k + 2]; }
+        sim += sxy / (fmax(sqrt(sxx), 1e-6) * fmax(sqrt(syy), 1e-6));
+    }
+    out[n] = sim / 5.0;
+}
+// frames of the dataset evaluation for VGG19: (N, 3, H, W) -> NHWC (pitch 4) with vgg_cosine_similarity.py:31-37's normalisation (v / range - 0.5) / (0.5 + 1e-6)
+__global__ __launch_bounds__(256) void k_metric_stage(const float* src, float* out, long npix, long hw, float range) {
+    for (long q = blockIdx.x * 256L + threadIdx.x; q < npix; q += (long)gridDim.x * 256) {
+        const long n = q / hw, p = q - n * hw;
+        const float* s = src + n * 3 * hw + p;
+        const float d = (float)(0.5 + 1e-6);
+        reinterpret_cast<float4*>(out)[q] = make_float4((s[0] / range - 0.5f) / d, (s[hw] / range - 0.5f) / d, (s[2 * hw] / range - 0.5f) / d, 0.f);
+    }
+}
 // ground-truth frames for the VGG19 branch: first 3 channels of observation t + t_off, bilinearly resized like F.interpolate(align_corners=False)
 // does for exact factors (losses.py:450): f = 2 -> 2x2 mean, f = 4 -> mean of the central 2x2 of each 4x4 block (same arithmetic as k_loss_l1)
 __global__ __launch_bounds__(256) void k_gt_resize(TV gt, float* out, int Ho, int Wo, long npix, int f, int t_off, int Tobs, int Trec) {
@@ -203,6 +245,15 @@ void launch_feat_l1_img(hipStream_t st, const T4& rec, const T4& gt, double* acc
     else if (rec.fmt) hipLaunchKernelGGL((k_feat_l1_img<true, false>), g, b, 0, st, r, t, n4, acc);
     else if (gt.fmt) hipLaunchKernelGGL((k_feat_l1_img<false, true>), g, b, 0, st, r, t, n4, acc);
     else hipLaunchKernelGGL((k_feat_l1_img<false, false>), g, b, 0, st, r, t, n4, acc);
+}
+int cos_blocks(const T4& f) { const long n4 = (long)f.H * f.W * (f.C / 4); return (int)(n4 / 1024 < 1 ? 1 : (n4 / 1024 > 64 ? 64 : n4 / 1024)); }
+void launch_feat_cos_img(hipStream_t st, const T4& x, const T4& y, double* part) {
+    const long n4 = (long)x.H * x.W * (x.C / 4);
+    const dim3 g(cos_blocks(x), x.N), b(256);
+    if (x.fmt && y.fmt) hipLaunchKernelGGL((k_feat_cos_img<true, true>), g, b, 0, st, x.d, y.d, n4, part);
+    else if (x.fmt) hipLaunchKernelGGL((k_feat_cos_img<true, false>), g, b, 0, st, x.d, y.d, n4, part);
+    else if (y.fmt) hipLaunchKernelGGL((k_feat_cos_img<false, true>), g, b, 0, st, x.d, y.d, n4, part);
+    else hipLaunchKernelGGL((k_feat_cos_img<false, false>), g, b, 0, st, x.d, y.d, n4, part);
 }
 void launch_maxpool_bwd(hipStream_t st, const T4& pre, const float* gp, bool gz_s16) {
     const long n4 = (long)pre.N * ((pre.H + 1) / 2) * ((pre.W + 1) / 2) * (pre.C / 4);
@@ -597,6 +648,40 @@ int vgg_eval_per_frame(caddy_ctx* c, double* out_host) {
     hipMemcpyAsync(out_host, acc, sizeof(double) * 5 * (size_t)N, hipMemcpyDeviceToHost, st);
     hipStreamSynchronize(st);
     for (int l = 0; l < 5; l++) { const double numel = (double)tr[l].H * tr[l].W * tr[l].C; for (int n = 0; n < N; n++) out_host[(size_t)l * N + n] /= numel; }
+    c->act.off = mark;
+    return c->fail ? -1 : 0;
+}
+
+// Dataset evaluation (evaluation/metrics/vgg_cosine_similarity.py:22-57, on a metrics context: caddy_metrics_ctx_create): the VGG19 cosine similarity of frames [0, nf) of
+// `ref` / `gen` ((nf, 3, H, W) fp32), out[n] = mean over relu1_1 .. relu5_1 of cos(f_l(ref_n), f_l(gen_n)).  Same walk of the activation arena as vgg_eval_per_frame; with c->dry
+// nothing is launched (workspace sizing).
+int vgg_metric_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, float range, double* out) {
+    const bool dry = c->dry;
+    const int H = c->cfg.height, W = c->cfg.width;
+    hipStream_t st = c->stream;
+    const size_t mark = c->act.off;
+    const int tc[5] = {64, 128, 256, 512, 512};
+    T4 gr = valloc(c, nf, H, W, 3), gg = valloc(c, nf, H, W, 3);
+    const long npix = (long)nf * H * W;
+    if (!dry) {
+        hipLaunchKernelGGL(k_metric_stage, dim3(grid_for(npix)), dim3(256), 0, st, ref, gr.d, npix, (long)H * W, range);
+        hipLaunchKernelGGL(k_metric_stage, dim3(grid_for(npix)), dim3(256), 0, st, gen, gg.d, npix, (long)H * W, range);
+    }
+    T4 tr[5], tg[5];
+    { int h = H, w = W; for (int l = 0; l < 5; l++) { tr[l] = valloc(c, nf, h, w, tc[l]); tg[l] = valloc(c, nf, h, w, tc[l]); h /= 2; w /= 2; } }
+    CosLevels lv{};
+    long total = 0;
+    for (int l = 0; l < 5; l++) { lv.off[l] = total; lv.blocks[l] = cos_blocks(tr[l]); total += (long)nf * lv.blocks[l] * 3; }
+    double* part = c->dalloc((size_t)total);
+    const size_t mark2 = c->act.off;
+    { Branch Rb{}; vgg_forward(c, gr, Rb, tr, false); for (int i = 0; i < VGG_NCONV; i++) if (VGG[i].tap >= 0) tr[VGG[i].tap].fmt = Rb.a[i].fmt; }
+    c->act.off = mark2;
+    { Branch Gb{}; vgg_forward(c, gg, Gb, tg, false); for (int i = 0; i < VGG_NCONV; i++) if (VGG[i].tap >= 0) tg[VGG[i].tap].fmt = Gb.a[i].fmt; }
+    if (c->act.overflow()) { c->act.off = mark; set_error("caddy_frame_metrics: workspace too small"); return -1; }
+    if (!dry) {
+        for (int l = 0; l < 5; l++) launch_feat_cos_img(st, tr[l], tg[l], part + lv.off[l]);
+        hipLaunchKernelGGL(k_feat_cos_finalize, dim3((nf + 63) / 64), dim3(64), 0, st, (const double*)part, lv, nf, out);
+    }
     c->act.off = mark;
     return c->fail ? -1 : 0;
 }

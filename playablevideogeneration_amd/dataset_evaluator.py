@@ -1,0 +1,82 @@
+"""Dataset evaluation: a reference dataset against a generated one (evaluation/dataset_evaluator.py:29-256), the `config["evaluation"]["evaluator"]`
+seam of evaluate_dataset.py (factory `evaluator(config, logger, reference_dataset, generated_dataset)`, `.compute_metrics()` -> the dict written to data.yml).
+
+Per frame, on the device: mse, motion_masked_mse, psnr, ssim and -- when VGG19 weights are configured (`evaluation.vgg19_weights` or
+`evaluation.vgg19_from_torchvision`, the loader of Trainer._find_vgg_weights) -- vgg_sim, all from one fused HIP pass (metrics.FrameMetrics).  The
+keys are those of compute_positional_statistics: {m}/avg, {m}/var, {m}/{i}, {m}/{i}/var.  LPIPS, FID, FVD, IS, the detector-based metrics, action
+variance / accuracy and the plots need pretrained networks or detectors that are not available and are not computed.
+"""
+from typing import Dict
+
+import numpy as np
+import torch
+
+from . import metrics as M
+
+METRICS = ("mse", "motion_masked_mse", "psnr", "ssim", "vgg_sim")
+
+
+class DatasetEvaluator:
+    def __init__(self, config, logger, reference_dataset, generated_dataset):
+        from torch.utils.data import DataLoader
+        from .batching import single_batch_elements_collate_fn
+        from .trainer import Trainer
+        self.config, self.logger = config, logger
+        self.reference_dataset, self.generated_dataset = reference_dataset, generated_dataset
+        b = config["evaluation"]["batching"]
+        self.reference_dataloader = DataLoader(reference_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=single_batch_elements_collate_fn,
+                                               num_workers=b.get("num_workers", 0), pin_memory=torch.cuda.is_available())
+        self.generated_dataloader = DataLoader(generated_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=single_batch_elements_collate_fn,
+                                               num_workers=b.get("num_workers", 0), pin_memory=torch.cuda.is_available())
+        if len(self.reference_dataloader) != len(self.generated_dataloader):
+            raise Exception(f"Reference and generated datasets should have the same sequences, but their length differs:"
+                            f"Reference ({len(self.reference_dataloader)}), Generated({len(self.generated_dataloader)})")
+        self.vgg_state = Trainer._find_vgg_weights(config["evaluation"])
+        if self.vgg_state is None:
+            self.logger.print("- vgg_sim skipped: no VGG19 weights configured (evaluation.vgg19_weights / evaluation.vgg19_from_torchvision)")
+        self.logger.print("- lpips, fid, fvd, inception score, detection metrics, action variance / accuracy and plots are not computed: "
+                          "they need pretrained networks or detectors that are not available")
+
+    @staticmethod
+    def check_range(values: Dict[str, torch.Tensor], which: str):
+        M.check_range(values, which)
+
+    @staticmethod
+    def compute_positional_statistics(values: np.ndarray, prefix: str) -> Dict:
+        """evaluation/dataset_evaluator.py:85-113"""
+        results = {}
+        positional_values = values.mean(axis=0)
+        positional_variances = values.var(axis=0).tolist()
+        global_variance = float(positional_values.var())
+        positional_values = positional_values.tolist()
+        global_value = float(sum(positional_values) / len(positional_values))
+        results[f"{prefix}/avg"] = global_value
+        results[f"{prefix}/var"] = global_variance
+        for idx, current_value in enumerate(positional_values):
+            results[f"{prefix}/{idx}"] = current_value
+        for idx, current_variance in enumerate(positional_variances):
+            results[f"{prefix}/{idx}/var"] = current_variance
+        return results
+
+    def compute_metrics(self) -> Dict:
+        names = [m for m in METRICS if m != "vgg_sim" or self.vgg_state is not None]
+        acc = {m: [] for m in names}
+        batches = len(self.reference_dataloader)
+        with torch.no_grad():
+            for idx, (reference_batch, generated_batch) in enumerate(zip(self.reference_dataloader, self.generated_dataloader)):
+                self.logger.print(f"- Computing metrics for batch [{idx}/{batches}]")
+                reference_observations = reference_batch.to_tuple(cuda=False)[0]
+                generated_observations = generated_batch.to_tuple(cuda=False)[0]
+                values = M.frame_metrics(reference_observations, generated_observations, 1.0, self.vgg_state)
+                self.check_range(values, "ref")
+                self.check_range(values, "gen")
+                for m in names:
+                    acc[m].append(values[m].numpy())
+        results = {}
+        for m in names:
+            results.update(self.compute_positional_statistics(np.concatenate(acc[m], axis=0), m))
+        return results
+
+
+def evaluator(config, logger, reference_dataset, generated_dataset):
+    return DatasetEvaluator(config, logger, reference_dataset, generated_dataset)

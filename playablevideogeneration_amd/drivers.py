@@ -5,6 +5,7 @@ display / wandb / ffmpeg plumbing, on the plugin seam the reference itself uses 
     python -m playablevideogeneration_amd.drivers play        --config cfg.yaml --actions 1,3,3,2 [--out play_results] [--sample 0:0]
     python -m playablevideogeneration_amd.drivers interpolate --config cfg.yaml --first 1 --second 2 [--steps 6] [--frames 8]
     python -m playablevideogeneration_amd.drivers build-dataset --config cfg.yaml
+    python -m playablevideogeneration_amd.drivers evaluate      --config eval.yaml
 
     train        train.py:76-108      epochs of trainer.train_epoch, `latest` checkpoint after each, `checkpoint_<step>` every save_freq steps, evaluation with the inferred
                                       actions every eval_freq steps and -- when the data carries annotations -- with the ground-truth actions mapped through the Hungarian
@@ -14,6 +15,9 @@ display / wandb / ffmpeg plumbing, on the plugin seam the reference itself uses 
     interpolate  interpolate.py:102-158  one sequence per interpolation value in linspace(0, 1, steps + 1) through generate_next_interpolation
     build-dataset  build_evaluation_dataset.py:17-77  the `builder(config, dataset, logger)` factory of config["evaluation_dataset"]["builder"] on the TEST split: roll-outs with
                                       one-hot actions and zero variations, written in the on-disk video format under logging.evaluation_dataset_directory
+    evaluate     evaluate_dataset.py:22-64  an EVALUATION config (configs/evaluation/*.yaml: reference_data / generated_data / data.target_input_size /
+                                      evaluation.batching): both datasets through the evaluation transform, the `evaluator(config, logger, reference, generated)`
+                                      factory of evaluation.evaluator (playablevideogeneration_amd.dataset_evaluator), its metrics as logging.output_root/run_name/data.yml
 
 The configuration defaults and directory layout are those of utils/configuration.py:31-110.  The model runs on the GPU through libcaddy_hip.so; there is no CPU path
 (the `*_loop` functions take the model object so that the tests can drive them with the emulator build of the same kernels).
@@ -254,6 +258,49 @@ def _load_for_inference(config, logger, required=True):
     return model, datasets
 
 
+DEFAULT_DATASET_EVALUATOR = "playablevideogeneration_amd.dataset_evaluator"
+
+
+def load_evaluation_configuration(path: str, create_directories: bool = True) -> Dict:
+    """utils/evaluation_configuration.py: both data roots must exist; logging.output_directory = output_root/run_name (+ images, evaluation_images)"""
+    import yaml
+    with open(path) as f:
+        config = yaml.safe_load(f)
+    for key in ("reference_data", "generated_data"):
+        if not os.path.isdir(config[key]["data_root"]):
+            raise Exception(f"Data directory {config[key]['data_root']} does not exist")
+    log = config["logging"]
+    log["output_directory"] = os.path.join(log["output_root"], log["run_name"])
+    log["output_images_directory"] = os.path.join(log["output_directory"], "images")
+    log["evaluation_images_directory"] = os.path.join(log["output_directory"], "evaluation_images")
+    if create_directories:
+        for key in ("output_directory", "output_images_directory", "evaluation_images_directory"):
+            os.makedirs(log[key], exist_ok=True)
+    return config
+
+
+def evaluate_loop(config, logger) -> Dict:
+    """evaluate_dataset.py:34-64 -> the metrics dict, also written to <output_directory>/data.yml"""
+    import yaml
+    from .video_dataset import VideoDataset, evaluation_transform
+    size = config["data"]["target_input_size"]
+    logger.print("- Loading datasets")
+    reference = VideoDataset(config["reference_data"]["data_root"], config["evaluation"]["batching"], evaluation_transform(config["reference_data"].get("crop"), size))
+    generated = VideoDataset(config["generated_data"]["data_root"], config["evaluation"]["batching"], evaluation_transform(config["generated_data"].get("crop"), size))
+    logger.print("- Creating evaluator")
+    path = config["evaluation"].get("evaluator", DEFAULT_DATASET_EVALUATOR)
+    if path.startswith("evaluation.dataset_evaluator"):      # the reference's own evaluator modules: this package's evaluator takes their place
+        path = DEFAULT_DATASET_EVALUATOR
+    ev = _factory(path, "evaluator")(config, logger, reference, generated)
+    logger.print("===== Computing metrics =====")
+    metrics = ev.compute_metrics()
+    logger.print("===== Computing metrics finished =====")
+    logger.print(metrics)
+    with open(os.path.join(config["logging"]["output_directory"], "data.yml"), "w") as f:
+        yaml.dump(metrics, f)
+    return metrics
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -263,7 +310,12 @@ def main(argv=None) -> int:
     p = sub.add_parser("interpolate"); p.add_argument("--config", required=True); p.add_argument("--first", type=int, required=True); p.add_argument("--second", type=int, required=True)
     p.add_argument("--steps", type=int, default=6); p.add_argument("--frames", type=int, default=8); p.add_argument("--out", default=None)
     p = sub.add_parser("build-dataset"); p.add_argument("--config", required=True)
+    p = sub.add_parser("evaluate"); p.add_argument("--config", required=True)
     args = ap.parse_args(argv)
+    if args.cmd == "evaluate":
+        config = load_evaluation_configuration(args.config)
+        evaluate_loop(config, HeadlessLogger(config))
+        return 0
     config = load_configuration(args.config)
     logger = HeadlessLogger(config)
     if args.cmd == "train":

@@ -1,7 +1,17 @@
-"""Frame-quality metrics of the paper's evaluation protocol that need no third-party network: per-observation MSE and
-PSNR between a reference and a generated sequence, the contracts of `evaluation/metrics/mse.py:13-24` and `evaluation/metrics/psnr.py:11-31`.
+"""Frame-quality metrics of the paper's evaluation protocol that need no third-party network.
 Inputs are (bs, observations_count, channels, height, width) tensors in the same value range; results are (bs, observations_count).
+
+    mse / psnr                  evaluation/metrics/mse.py:13-24, psnr.py:11-31 -- plain torch expressions
+    ssim                        evaluation/metrics/ssim.py:13-35 (piq.ssim)                            \
+    motion_masked_mse           evaluation/metrics/motion_masked_mse.py:16-28 + motion_mask.py:14-37    > the fused HIP pass of csrc/frame_metrics.hip
+    vgg_cosine_similarity       evaluation/metrics/vgg_cosine_similarity.py:22-57 (VGG19 relu1_1..5_1)  /  (+ the VGG19 kernels of csrc/perceptual.hip)
+
+The HIP-backed metrics run on a metrics context of libcaddy_hip.so (caddy_metrics_ctx_create), cached per frame geometry; there is no torch fallback.
+`set_library` points them at another build of the same kernels (the tests' host simulator).
 (FID / FVD / LPIPS / detector-based metrics depend on pretrained networks and stay out of scope.)"""
+import ctypes as C
+from typing import Dict
+
 import torch
 
 
@@ -13,6 +23,152 @@ def psnr(reference_observations: torch.Tensor, generated_observations: torch.Ten
     """-10 log10(MSE of the range-normalised frames + 1e-8): the reference's stabilising constant caps the score at 80 dB"""
     err = torch.mean(((reference_observations - generated_observations) / value_range) ** 2, dim=[2, 3, 4])
     return -10.0 * torch.log10(err + 1e-8)
+
+
+# ---- HIP-backed metrics (caddy_frame_metrics) ----
+SLOTS = ("mse", "motion_masked_mse", "psnr", "ssim", "vgg_sim", "ref_min", "ref_max", "gen_min", "gen_max")      # CADDY_FM_* of include/caddy_hip.h
+VGG_FRAMES_256 = 30      # frames per VGG19 chunk at 256 x 256 (scaled by the frame area): ~4 GB of feature maps
+_default_lib = None
+_contexts: Dict = {}
+
+
+def set_library(lib) -> None:
+    """library the HIP-backed metrics use when none is passed (None: libcaddy_hip.so); drops the cached contexts"""
+    global _default_lib
+    _default_lib = lib
+    _contexts.clear()
+
+
+def _bind(lib):
+    from .engine import _bind as bind_engine
+    lib = bind_engine(lib)
+    if not getattr(lib, "_caddy_metrics_bound", False):
+        lib.caddy_metrics_workspace_bytes.restype = C.c_size_t
+        lib.caddy_metrics_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.caddy_metrics_ctx_create.restype = C.c_void_p
+        lib.caddy_metrics_ctx_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        lib.caddy_frame_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]
+        lib._caddy_metrics_bound = True
+    return lib
+
+
+class FrameMetrics:
+    """A metrics context for frames of height x width: the fused per-frame pass and, with `vgg_state_dict` (torchvision vgg19 naming, as
+    Engine.load_vgg takes it), the VGG19 cosine similarity.  Calls with more than `max_frames` frames run in chunks of `max_frames`."""
+
+    def __init__(self, height: int, width: int, max_frames: int, vgg_state_dict=None, lib=None, device=None):
+        from . import _lib
+        from .engine import CaddyError
+        self.lib = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
+        kind = getattr(self.lib, "_caddy_device_type", "cuda")
+        self.device = torch.device(device) if device is not None else torch.device(kind)
+        self.H, self.W, self.max_frames, self.vgg = int(height), int(width), int(max_frames), vgg_state_dict is not None
+        self._err = lambda: self.lib.caddy_last_error().decode()
+        n = self.lib.caddy_metrics_workspace_bytes(self.max_frames, self.H, self.W, int(self.vgg))
+        if n == 0:
+            raise CaddyError(self._err())
+        raw = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+        self._ws = raw
+        self.ws_bytes = n
+        self.ctx = self.lib.caddy_metrics_ctx_create(self.max_frames, self.H, self.W, int(self.vgg), raw.data_ptr() + (-raw.data_ptr()) % 256, n)
+        if not self.ctx:
+            raise CaddyError(self._err())
+        if self.vgg:
+            from .engine import ParamInfo
+            info = ParamInfo()
+            flat = torch.zeros(self.lib.caddy_vgg_param_floats(), dtype=torch.float32, device=self.device)
+            for i in range(self.lib.caddy_vgg_param_count()):
+                self.lib.caddy_vgg_param_info_get(i, C.byref(info))
+                name, off, shape = info.name.decode(), info.offset, tuple(info.shape[:info.ndim])
+                key = name if name in vgg_state_dict else name[len("features."):]
+                if key not in vgg_state_dict:
+                    raise CaddyError(f"VGG19 state dict lacks {name}")
+                t = vgg_state_dict[key].detach().to(self.device, torch.float32)
+                if tuple(t.shape) != shape:
+                    raise CaddyError(f"VGG19 {name}: shape {tuple(t.shape)}, expected {shape}")
+                flat[off:off + t.numel()] = t.reshape(-1)
+            self._stream()
+            self._check(self.lib.caddy_load_vgg(self.ctx, flat.data_ptr()))
+            if self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).synchronize()
+
+    def _check(self, rc):
+        if rc != 0:
+            from .engine import CaddyError
+            raise CaddyError(self._err() or f"caddy error {rc}")
+
+    def _stream(self):
+        self.lib.caddy_set_stream(self.ctx, torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0)
+
+    def set_vgg_precision(self, forward: int):
+        """arithmetic of the VGG19 convolutions: 0 (exact fp32) | 16 (split f16, default) | 18 (plain f16)"""
+        self._check(self.lib.caddy_set_vgg_precision(self.ctx, int(forward), 17))
+
+    def __call__(self, reference_observations: torch.Tensor, generated_observations: torch.Tensor, value_range: float = 1.0,
+                 want_vgg: bool = False) -> Dict[str, torch.Tensor]:
+        """-> {slot: (bs, observations_count) float64 CPU tensor} for the slots of SLOTS (vgg_sim: NaN unless want_vgg)"""
+        r, g = reference_observations, generated_observations
+        if r.dim() != 5 or r.shape != g.shape or r.shape[2] != 3 or tuple(r.shape[3:]) != (self.H, self.W):
+            raise ValueError(f"expected two (bs, observations_count, 3, {self.H}, {self.W}) tensors, got {tuple(r.shape)} and {tuple(g.shape)}")
+        if want_vgg and not self.vgg:
+            raise ValueError("this metrics context was created without VGG19 weights")
+        B, T = int(r.shape[0]), int(r.shape[1])
+        r = r.detach().to(self.device, torch.float32).contiguous()
+        g = g.detach().to(self.device, torch.float32).contiguous()
+        out = torch.empty(len(SLOTS), B, T, dtype=torch.float64)
+        self._stream()
+        self._check(self.lib.caddy_frame_metrics(self.ctx, r.data_ptr(), g.data_ptr(), B, T, float(value_range), int(want_vgg), out.data_ptr()))
+        return {k: out[i] for i, k in enumerate(SLOTS)}
+
+    def __del__(self):
+        if getattr(self, "ctx", None):
+            if self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).synchronize()
+            self.lib.caddy_ctx_destroy(self.ctx)
+            self.ctx = None
+
+
+def check_range(values: Dict[str, torch.Tensor], which: str = "ref") -> None:
+    """DatasetEvaluator.check_range (evaluation/dataset_evaluator.py:73-83) from the per-frame minima / maxima of the fused pass"""
+    mx, mn = float(values[which + "_max"].max()), float(values[which + "_min"].min())
+    if mx > 1.0 or mn < 0.0:
+        raise Exception(f"Input tensor outside allowed range [0.0, 1.0]: [{mn}, {mx}]")
+
+
+def frame_metrics(reference_observations: torch.Tensor, generated_observations: torch.Tensor, value_range: float = 1.0, vgg_state_dict=None,
+                  lib=None) -> Dict[str, torch.Tensor]:
+    """every slot of SLOTS in one pass (vgg_sim only with `vgg_state_dict`); the metrics context is cached per frame geometry"""
+    B, T, _, H, W = reference_observations.shape
+    n = int(B) * int(T)
+    lib = lib if lib is not None else _default_lib
+    vkey = None if vgg_state_dict is None else id(vgg_state_dict)
+    key = (id(lib), str(reference_observations.device), int(H), int(W), vkey)
+    fm = _contexts.get(key)
+    want = n if vgg_state_dict is None else min(n, max(1, VGG_FRAMES_256 * 256 * 256 // (int(H) * int(W))))
+    if fm is None or (vgg_state_dict is None and fm.max_frames < min(n, 1024)):
+        _contexts.pop(key, None)
+        fm = FrameMetrics(H, W, min(want, 1024), vgg_state_dict, lib)
+        fm._keep = vgg_state_dict      # (the cache key holds its id)
+        _contexts[key] = fm
+    return fm(reference_observations, generated_observations, value_range, want_vgg=vgg_state_dict is not None)
+
+
+def ssim(reference_observations: torch.Tensor, generated_observations: torch.Tensor, value_range: float = 1.0, lib=None) -> torch.Tensor:
+    """piq.ssim(generated / range, reference / range, reduction="none") per observation (evaluation/metrics/ssim.py:13-35)"""
+    return frame_metrics(reference_observations, generated_observations, value_range, lib=lib)["ssim"]
+
+
+def motion_masked_mse(reference_observations: torch.Tensor, generated_observations: torch.Tensor, lib=None) -> torch.Tensor:
+    """MSE weighted by the frame-difference motion mask of the reference sequence (evaluation/metrics/motion_masked_mse.py:16-28)"""
+    return frame_metrics(reference_observations, generated_observations, lib=lib)["motion_masked_mse"]
+
+
+def vgg_cosine_similarity(reference_observations: torch.Tensor, generated_observations: torch.Tensor, vgg_state_dict, value_range: float = 1.0,
+                          lib=None) -> torch.Tensor:
+    """mean over relu1_1 .. relu5_1 of the cosine similarity of the VGG19 features (evaluation/metrics/vgg_cosine_similarity.py:22-57)"""
+    if vgg_state_dict is None:
+        raise ValueError("vgg_cosine_similarity needs VGG19 weights")
+    return frame_metrics(reference_observations, generated_observations, value_range, vgg_state_dict, lib=lib)["vgg_sim"]
 
 
 def rollout_quality(model, batch_tuple, ground_truth_observations_init: int = 1, gumbel_temperature: float = 1.0) -> dict:

@@ -88,6 +88,23 @@ def final_transform(config) -> Callable:
     return transform
 
 
+def evaluation_transform(crop, target_input_size) -> Callable:
+    """PIL image -> (3, H, W) fp32 tensor in [0, 1] for the dataset evaluation: crop ([left, upper, right, lower] or None), bilinear resize to
+    `target_input_size` ((width, height)) when the size differs, x / 255 -- no normalisation (TransformsGenerator.get_evaluation_transforms,
+    dataset/transforms.py:67-87: check_and_resize -> ToTensor -> / 1.0)."""
+    size = tuple(target_input_size)
+
+    def transform(image):
+        from PIL import Image
+        if crop is not None:
+            image = image.crop(crop)
+        if image.size != size:
+            image = image.resize(size, Image.BILINEAR)
+        x = torch.from_numpy(np.asarray(image.convert("RGB"), dtype=np.uint8).copy()).permute(2, 0, 1).contiguous()
+        return x.float().div(255) / 1.0
+    return transform
+
+
 class VideoDataset(Dataset):
     """Dataset of sampled sequences over a directory of videos (dataset/video_dataset.py:14-149).  `batching_config` is the reference's
     `training.batching` / `evaluation.batching` dict (observations_count, observation_stacking, skip_frames); `transform` maps a PIL frame to a
