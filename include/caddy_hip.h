@@ -140,6 +140,14 @@ caddy_ctx* caddy_metrics_ctx_create(int max_frames, int height, int width, int v
 int caddy_frame_metrics(caddy_ctx* ctx, const float* ref, const float* gen, int B, int T, float value_range, int want_vgg, double* out_host);
 enum { CADDY_FM_MSE, CADDY_FM_MOTION_MSE, CADDY_FM_PSNR, CADDY_FM_SSIM, CADDY_FM_VGG_SIM,
        CADDY_FM_REF_MIN, CADDY_FM_REF_MAX, CADDY_FM_GEN_MIN, CADDY_FM_GEN_MAX, CADDY_FM_COUNT };
+/* Breakout platform detector (evaluation/metrics/breakout_platform_position.py, BreakoutPlatformPosition.forward + detect_platform) on a metrics context:
+ * obs: (B, T, 3, height, width) fp32 device tensor in [0, 1]; out_host[b * T + t] (host memory, B * T int32) = the left edge of the platform in frame (b, t), or -1.
+ * Only channel 0 of row `row` is read (detect_platform reads frame[0, row, x]); a column is in the mask iff lo <= v <= hi (never for NaN), and the LAST column
+ * (x = width - 1) counts as outside it (the reference's `idx != width - 1`), so a run reaching the right edge ends at width - 2.  The result is the start of the
+ * first run of at least min_run masked columns (the reference: 12, `current_position_length > 11`).  The caller passes the reference's row int(188 / 208 * height)
+ * and its fp32 channel-0 bounds 100 / 255 - 0.15 and 200 / 255 + 0.15.  Errors (-2, caddy_last_error): a context not from caddy_metrics_ctx_create, null
+ * pointers, row outside [0, height), min_run < 1, width > 4096.  Runs in chunks of max_frames frames; one launch per chunk; deterministic; waits for the stream. */
+int caddy_platform_positions(caddy_ctx* ctx, const float* obs, int B, int T, int row, float lo, float hi, int min_run, int* out_host);
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

@@ -4,6 +4,7 @@
 // conv_mfma.hip / pointwise.hip / head.hip / pack.hip on one HIP stream; nothing here allocates device memory.
 #include "net.h"
 #include "frame_metrics.h"
+#include "detection.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1645,6 +1646,28 @@ int caddy_frame_metrics(caddy_ctx* c, const float* ref, const float* gen, int B,
         hipStreamSynchronize(st);
         for (int s = 0; s < FM_SLOTS; s++)
             for (int j = 0; j < nf; j++) out_host[s * N + n0 + j] = (s == CADDY_FM_VGG_SIM && !want_vgg) ? NAN : tmp[(size_t)s * M + j];
+    }
+    return finish(c);
+}
+
+int caddy_platform_positions(caddy_ctx* c, const float* obs, int B, int T, int row, float lo, float hi, int min_run, int* out_host) {
+    if (!c || !c->metrics_only) { set_error("caddy_platform_positions needs a context from caddy_metrics_ctx_create"); return -2; }
+    c->fail = false;
+    if (!obs || !out_host) { set_error("null input"); return -2; }
+    const int H = c->cfg.height, W = c->cfg.width;
+    if (B < 1 || T < 1) { set_error("caddy_platform_positions: B and T must be positive"); return -2; }
+    if (row < 0 || row >= H) { set_error("caddy_platform_positions: row outside the frame (0 <= row < height)"); return -2; }
+    if (min_run < 1) { set_error("caddy_platform_positions: min_run must be positive"); return -2; }
+    if (W > DET_MAX_W) { set_error("caddy_platform_positions: frames wider than 4096 columns"); return -2; }
+    const int M = c->cfg.batch;
+    const long N = (long)B * T;
+    hipStream_t st = c->stream;
+    int* dev = (int*)c->fm_out;      // (FM_SLOTS doubles = 72 bytes per frame: room for one int32 each)
+    for (long n0 = 0; n0 < N; n0 += M) {      // chunks of max_frames frames, as caddy_frame_metrics
+        const int nf = (int)std::min<long>(M, N - n0);
+        c->ck(det_platform_launch(obs, (int)n0, nf, H, W, row, lo, hi, min_run, dev, st), "platform positions");
+        hipMemcpyAsync(out_host + n0, dev, sizeof(int) * nf, hipMemcpyDeviceToHost, st);
+        hipStreamSynchronize(st);
     }
     return finish(c);
 }

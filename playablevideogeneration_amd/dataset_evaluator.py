@@ -3,8 +3,9 @@ seam of evaluate_dataset.py (factory `evaluator(config, logger, reference_datase
 
 Per frame, on the device: mse, motion_masked_mse, psnr, ssim and -- when VGG19 weights are configured (`evaluation.vgg19_weights` or
 `evaluation.vgg19_from_torchvision`, the loader of Trainer._find_vgg_weights) -- vgg_sim, all from one fused HIP pass (metrics.FrameMetrics).  The
-keys are those of compute_positional_statistics: {m}/avg, {m}/var, {m}/{i}, {m}/{i}/var.  LPIPS, FID, FVD, IS, the detector-based metrics, action
-variance / accuracy and the plots need pretrained networks or detectors that are not available and are not computed.
+keys are those of compute_positional_statistics: {m}/avg, {m}/var, {m}/{i}, {m}/{i}/var.  LPIPS, FID, FVD, IS and the plots need pretrained networks
+that are not available and are not computed.  The per-dataset evaluators that add the detection and action metrics of Breakout and BAIR are
+dataset_evaluator_breakout and dataset_evaluator_bair (ActionSpaceEvaluator below).
 """
 from typing import Dict
 
@@ -17,6 +18,9 @@ METRICS = ("mse", "motion_masked_mse", "psnr", "ssim", "vgg_sim")
 
 
 class DatasetEvaluator:
+    NOT_COMPUTED = ("- lpips, fid, fvd, inception score, detection metrics, action variance / accuracy and plots are not computed: "
+                    "they need pretrained networks or detectors that are not available")
+
     def __init__(self, config, logger, reference_dataset, generated_dataset):
         from torch.utils.data import DataLoader
         from .batching import single_batch_elements_collate_fn
@@ -34,8 +38,7 @@ class DatasetEvaluator:
         self.vgg_state = Trainer._find_vgg_weights(config["evaluation"])
         if self.vgg_state is None:
             self.logger.print("- vgg_sim skipped: no VGG19 weights configured (evaluation.vgg19_weights / evaluation.vgg19_from_torchvision)")
-        self.logger.print("- lpips, fid, fvd, inception score, detection metrics, action variance / accuracy and plots are not computed: "
-                          "they need pretrained networks or detectors that are not available")
+        self.logger.print(self.NOT_COMPUTED)
 
     @staticmethod
     def check_range(values: Dict[str, torch.Tensor], which: str):
@@ -75,6 +78,79 @@ class DatasetEvaluator:
         results = {}
         for m in names:
             results.update(self.compute_positional_statistics(np.concatenate(acc[m], axis=0), m))
+        return results
+
+
+class ActionSpaceEvaluator(DatasetEvaluator):
+    """The loop of the reference's per-dataset evaluators (evaluation/dataset_evaluator_breakout.py, dataset_evaluator_bair.py): per frame mse, psnr,
+    ssim (and vgg_sim with VGG19 weights; no motion_masked_mse, as there), plus the action variance and action accuracy of the inferred actions of the
+    generated sequences against the movement that follows each of them in the reference sequences.  Subclasses say how a movement is measured
+    (`movements`) and may add detections (`detect`, `detection_results`)."""
+    NOT_COMPUTED = "- lpips, fid, fvd and the density plots are not computed: they need pretrained networks that are not available"
+    FRAME_METRICS = ("mse", "psnr", "ssim", "vgg_sim")
+
+    def detect(self, reference_observations: torch.Tensor, generated_observations: torch.Tensor) -> Dict[str, np.ndarray]:
+        """per-batch detections to accumulate: {name: (bs, observations_count) array}"""
+        return {}
+
+    def movements(self, reference_batch, detections: Dict[str, np.ndarray], observations_count: int) -> np.ndarray:
+        """-> (bs, observations_count - 1, vector_size): the movement of each transition of the reference sequences"""
+        raise NotImplementedError
+
+    def detection_results(self, detections: Dict[str, np.ndarray]) -> Dict:
+        return {}
+
+    @staticmethod
+    def sequence_name(batch, sequence_idx: int) -> str:
+        return str(getattr(batch.video[sequence_idx], "frames_path", sequence_idx))
+
+    def inferred_actions(self, generated_batch, observations_count: int) -> np.ndarray:
+        """(bs, observations_count - 1): metadata[i]["inferred_action"] of every transition of the generated sequences"""
+        rows = []
+        for b, video in enumerate(generated_batch.video):
+            meta = video.metadata
+            if len(meta) - 1 != observations_count - 1:
+                raise Exception(f"Generated sequence {self.sequence_name(generated_batch, b)} has {len(meta) - 1} transitions in its metadata, but the "
+                                f"evaluated sequences have {observations_count - 1}")
+            if any("inferred_action" not in m for m in meta[:-1]):
+                raise Exception(f"Generated sequence {self.sequence_name(generated_batch, b)} has metadata without an inferred_action")
+            rows.append([m["inferred_action"] for m in meta[:-1]])
+        return np.asarray(rows)
+
+    def compute_metrics(self) -> Dict:
+        from . import action_metrics as A
+        names = [m for m in self.FRAME_METRICS if m != "vgg_sim" or self.vgg_state is not None]
+        acc = {m: [] for m in names}
+        detections, actions, movements = {}, [], []
+        device = M.device()
+        batches = len(self.reference_dataloader)
+        with torch.no_grad():
+            for idx, (reference_batch, generated_batch) in enumerate(zip(self.reference_dataloader, self.generated_dataloader)):
+                self.logger.print(f"- Computing metrics for batch [{idx}/{batches}]")
+                reference_observations = reference_batch.to_tuple(cuda=False)[0].to(device)
+                generated_observations = generated_batch.to_tuple(cuda=False)[0].to(device)
+                values = M.frame_metrics(reference_observations, generated_observations, 1.0, self.vgg_state)
+                self.check_range(values, "ref")
+                self.check_range(values, "gen")
+                for m in names:
+                    acc[m].append(values[m].numpy())
+                found = self.detect(reference_observations, generated_observations)
+                for k, v in found.items():
+                    detections.setdefault(k, []).append(v)
+                T = int(reference_observations.shape[1])
+                actions.append(self.inferred_actions(generated_batch, T))
+                movements.append(self.movements(reference_batch, found, T))
+        results = {}
+        for m in names:
+            results.update(self.compute_positional_statistics(np.concatenate(acc[m], axis=0), m))
+        results.update(self.detection_results({k: np.concatenate(v, axis=0) for k, v in detections.items()}))
+        actions, movements = np.concatenate(actions, axis=0), np.concatenate(movements, axis=0)
+        actions_count = self.config["data"]["actions_count"]
+        results.update(A.action_variance(actions, movements, actions_count))
+        accuracy = A.action_classification_score(actions, movements, actions_count)
+        if not accuracy:
+            self.logger.print("- Warning: action accuracy results could not be computed")
+        results.update(accuracy)
         return results
 
 

@@ -1,0 +1,33 @@
+"""Breakout dataset evaluation (evaluation/dataset_evaluator_breakout.py): the frame metrics of DatasetEvaluator plus the platform detector.
+
+The platform's left edge is found in every reference and generated frame on the device (metrics.breakout_platform_positions, csrc/detection.hip).
+detection/* compares the two (action_metrics.detection_metric_1d); the movement that follows each inferred action is the change of the REFERENCE
+platform position, -1 detections included as the reference leaves them, and feeds action_variance/* and the action accuracy keys.
+Select it with evaluation.evaluator: playablevideogeneration_amd.dataset_evaluator_breakout."""
+from typing import Dict
+
+import numpy as np
+import torch
+
+from . import action_metrics as A
+from . import metrics as M
+from .dataset_evaluator import ActionSpaceEvaluator
+
+
+class DatasetEvaluatorBreakout(ActionSpaceEvaluator):
+
+    def detect(self, reference_observations: torch.Tensor, generated_observations: torch.Tensor) -> Dict[str, np.ndarray]:
+        return {"reference": M.breakout_platform_positions(reference_observations),
+                "generated": M.breakout_platform_positions(generated_observations)}
+
+    def movements(self, reference_batch, detections: Dict[str, np.ndarray], observations_count: int) -> np.ndarray:
+        positions = detections["reference"]
+        return (positions[:, 1:] - positions[:, :-1])[..., None]
+
+    def detection_results(self, detections: Dict[str, np.ndarray]) -> Dict:
+        self.logger.print("- Computing detection score")
+        return A.detection_metric_1d(detections["reference"], detections["generated"], "detection")
+
+
+def evaluator(config, logger, reference_dataset, generated_dataset):
+    return DatasetEvaluatorBreakout(config, logger, reference_dataset, generated_dataset)

@@ -5,13 +5,15 @@ Inputs are (bs, observations_count, channels, height, width) tensors in the same
     ssim                        evaluation/metrics/ssim.py:13-35 (piq.ssim)                            \
     motion_masked_mse           evaluation/metrics/motion_masked_mse.py:16-28 + motion_mask.py:14-37    > the fused HIP pass of csrc/frame_metrics.hip
     vgg_cosine_similarity       evaluation/metrics/vgg_cosine_similarity.py:22-57 (VGG19 relu1_1..5_1)  /  (+ the VGG19 kernels of csrc/perceptual.hip)
+    breakout_platform_positions evaluation/metrics/breakout_platform_position.py                       -- the row scan of csrc/detection.hip
 
 The HIP-backed metrics run on a metrics context of libcaddy_hip.so (caddy_metrics_ctx_create), cached per frame geometry; there is no torch fallback.
 `set_library` points them at another build of the same kernels (the tests' host simulator).
-(FID / FVD / LPIPS / detector-based metrics depend on pretrained networks and stay out of scope.)"""
+(FID / FVD / LPIPS and the Tennis detector depend on pretrained networks and stay out of scope.)"""
 import ctypes as C
 from typing import Dict
 
+import numpy as np
 import torch
 
 
@@ -48,6 +50,7 @@ def _bind(lib):
         lib.caddy_metrics_ctx_create.restype = C.c_void_p
         lib.caddy_metrics_ctx_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         lib.caddy_frame_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]
+        lib.caddy_platform_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p]
         lib._caddy_metrics_bound = True
     return lib
 
@@ -120,6 +123,20 @@ class FrameMetrics:
         self._check(self.lib.caddy_frame_metrics(self.ctx, r.data_ptr(), g.data_ptr(), B, T, float(value_range), int(want_vgg), out.data_ptr()))
         return {k: out[i] for i, k in enumerate(SLOTS)}
 
+    def platform_positions(self, observations: torch.Tensor, row: int, lo: float, hi: float, min_run: int) -> np.ndarray:
+        """-> (bs, observations_count) int64: the start of the first run of >= min_run columns of row `row` whose channel-0 value lies in [lo, hi]
+        (the last column never counts), -1 where there is none (caddy_platform_positions)"""
+        o = observations
+        if o.dim() != 5 or o.shape[2] != 3 or tuple(o.shape[3:]) != (self.H, self.W):
+            raise ValueError(f"expected a (bs, observations_count, 3, {self.H}, {self.W}) tensor, got {tuple(o.shape)}")
+        B, T = int(o.shape[0]), int(o.shape[1])
+        o = o.detach().to(self.device, torch.float32).contiguous()
+        out = np.empty((B, T), dtype=np.int32)
+        self._stream()
+        self._check(self.lib.caddy_platform_positions(self.ctx, o.data_ptr(), B, T, int(row), float(lo), float(hi), int(min_run),
+                                                      out.ctypes.data_as(C.c_void_p)))
+        return out.astype(np.int64)
+
     def __del__(self):
         if getattr(self, "ctx", None):
             if self.device.type == "cuda":
@@ -135,14 +152,13 @@ def check_range(values: Dict[str, torch.Tensor], which: str = "ref") -> None:
         raise Exception(f"Input tensor outside allowed range [0.0, 1.0]: [{mn}, {mx}]")
 
 
-def frame_metrics(reference_observations: torch.Tensor, generated_observations: torch.Tensor, value_range: float = 1.0, vgg_state_dict=None,
-                  lib=None) -> Dict[str, torch.Tensor]:
-    """every slot of SLOTS in one pass (vgg_sim only with `vgg_state_dict`); the metrics context is cached per frame geometry"""
-    B, T, _, H, W = reference_observations.shape
+def _cached_context(observations: torch.Tensor, vgg_state_dict, lib) -> FrameMetrics:
+    """the metrics context of this library, device, frame geometry and VGG19 weights, (re)created when it holds too few frames"""
+    B, T, _, H, W = observations.shape
     n = int(B) * int(T)
     lib = lib if lib is not None else _default_lib
     vkey = None if vgg_state_dict is None else id(vgg_state_dict)
-    key = (id(lib), str(reference_observations.device), int(H), int(W), vkey)
+    key = (id(lib), str(observations.device), int(H), int(W), vkey)
     fm = _contexts.get(key)
     want = n if vgg_state_dict is None else min(n, max(1, VGG_FRAMES_256 * 256 * 256 // (int(H) * int(W))))
     if fm is None or (vgg_state_dict is None and fm.max_frames < min(n, 1024)):
@@ -150,7 +166,38 @@ def frame_metrics(reference_observations: torch.Tensor, generated_observations: 
         fm = FrameMetrics(H, W, min(want, 1024), vgg_state_dict, lib)
         fm._keep = vgg_state_dict      # (the cache key holds its id)
         _contexts[key] = fm
+    return fm
+
+
+def frame_metrics(reference_observations: torch.Tensor, generated_observations: torch.Tensor, value_range: float = 1.0, vgg_state_dict=None,
+                  lib=None) -> Dict[str, torch.Tensor]:
+    """every slot of SLOTS in one pass (vgg_sim only with `vgg_state_dict`); the metrics context is cached per frame geometry"""
+    fm = _cached_context(reference_observations, vgg_state_dict, lib)
     return fm(reference_observations, generated_observations, value_range, want_vgg=vgg_state_dict is not None)
+
+
+def breakout_platform_parameters(height: int):
+    """(row, lo, hi, min_run) of BreakoutPlatformPosition (evaluation/metrics/breakout_platform_position.py): the platform row int(188 / 208 * height),
+    the fp32 channel-0 bounds of its colour mask (torch's float32 arithmetic, as the reference computes them) and the run length of detect_platform"""
+    lo = float(torch.tensor([100], dtype=torch.float) / 255 - 0.15)
+    hi = float(torch.tensor([200], dtype=torch.float) / 255 + 0.15)
+    return int(188 / 208 * int(height)), lo, hi, 12
+
+
+def breakout_platform_positions(observations: torch.Tensor, lib=None) -> np.ndarray:
+    """(bs, observations_count, 3, H, W) frames in [0, 1] -> (bs, observations_count) int64 left edge of the Breakout platform, -1 where it is not
+    found (BreakoutPlatformPosition.forward); runs on the metrics context frame_metrics caches for this geometry"""
+    if observations.dim() != 5:
+        raise ValueError(f"expected a (bs, observations_count, 3, H, W) tensor, got {tuple(observations.shape)}")
+    row, lo, hi, min_run = breakout_platform_parameters(observations.shape[3])
+    return _cached_context(observations, None, lib).platform_positions(observations, row, lo, hi, min_run)
+
+
+def device(lib=None) -> torch.device:
+    """the torch device the pointers of `lib` (default: the library of the HIP-backed metrics) live on"""
+    from . import _lib
+    lib = lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load())
+    return torch.device(getattr(lib, "_caddy_device_type", "cuda"))
 
 
 def ssim(reference_observations: torch.Tensor, generated_observations: torch.Tensor, value_range: float = 1.0, lib=None) -> torch.Tensor:
