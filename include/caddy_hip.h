@@ -148,6 +148,24 @@ enum { CADDY_FM_MSE, CADDY_FM_MOTION_MSE, CADDY_FM_PSNR, CADDY_FM_SSIM, CADDY_FM
  * and its fp32 channel-0 bounds 100 / 255 - 0.15 and 200 / 255 + 0.15.  Errors (-2, caddy_last_error): a context not from caddy_metrics_ctx_create, null
  * pointers, row outside [0, height), min_run < 1, width > 4096.  Runs in chunks of max_frames frames; one launch per chunk; deterministic; waits for the stream. */
 int caddy_platform_positions(caddy_ctx* ctx, const float* obs, int B, int T, int row, float lo, float hi, int min_run, int* out_host);
+/* --- LPIPS of the dataset evaluation (evaluation/metrics/lpips.py:14,33: lpips.LPIPS(net='vgg') per observation, called from evaluation/dataset_evaluator*.py).  An LPIPS
+ *     context is a metrics context of its own kind: the VGG16 trunk up to relu5_3 on the library's VGG convolution kernels (arithmetic through caddy_set_vgg_precision, the
+ *     per-layer f16 range guard as for VGG19) plus the five learned 1x1 "lin" layers; frames of height x width, both multiples of 16 (else 0 / NULL and caddy_last_error), in
+ *     chunks of max_frames frames.  caddy_frame_metrics and caddy_load_vgg refuse an LPIPS context, caddy_frame_lpips and caddy_load_lpips any other.  Destroy with caddy_ctx_destroy. --- */
+size_t caddy_lpips_workspace_bytes(int max_frames, int height, int width);                                  /* evaluation/metrics/lpips.py:14 */
+caddy_ctx* caddy_lpips_ctx_create(int max_frames, int height, int width, void* workspace, size_t bytes);    /* evaluation/metrics/lpips.py:14 */
+/* the network's tensors (evaluation/metrics/lpips.py:14): features.{idx}.weight / .bias of torchvision's vgg16 for the 13 convolutions (idx 0 2 5 7 10 12 14 17 19 21 24 26 28),
+ * then lin{l}.model.1.weight (1, C_l, 1, 1), l = 0..4; caddy_load_lpips takes a device buffer laid out by their offsets */
+int caddy_lpips_param_count(void);
+int caddy_lpips_param_info_get(int index, caddy_param_info* out);
+long caddy_lpips_param_floats(void);
+int caddy_load_lpips(caddy_ctx* ctx, const float* lpips_flat);
+/* evaluation/metrics/lpips.py:33: ref / gen as for caddy_frame_metrics, values in [0, value_range] (the package's normalize=True maps them to [-1, 1], then its scaling
+ * layer).  out_host (host memory, 6 * B * T doubles): out_host[n] = LPIPS(ref_n, gen_n), out_host[(1 + l) * N + n] = its term of level l (relu1_2, 2_2, 3_3, 4_3, 5_3):
+ * the mean over the pixels of sum_c w_c (f0_c / (|f0| + 1e-10) - f1_c / (|f1| + 1e-10))^2.  Deterministic (no float atomics); identical frames give exactly 0.  Waits for the stream. */
+int caddy_frame_lpips(caddy_ctx* ctx, const float* ref, const float* gen, int B, int T, float value_range, double* out_host);
+/* tests: bit l set = the level-l feature maps of both frames travelled as S16 tensors in some chunk of the last caddy_frame_lpips (evaluation/metrics/lpips.py:33); -1: no LPIPS context */
+int caddy_debug_lpips_tap_formats(caddy_ctx* ctx);
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

@@ -1598,7 +1598,94 @@ static void metrics_sizes(int max_frames, int H, int W, int vgg, size_t* persist
     delete c;
 }
 
+// LPIPS context of the dataset evaluation (caddy_lpips_ctx_create; evaluation/metrics/lpips.py:14,33): a metrics context whose VGG state is the VGG16-to-relu5_3 trunk plus the five
+// lin vectors; the activation arena of one chunk of vgg_lpips_chunk's walk and 6 x max_frames result doubles
+#define LPIPS_ROWS 6
+static bool lpips_args_ok(int max_frames, int H, int W) {
+    if (max_frames < 1 || H < 1 || W < 1) { set_error("caddy_lpips: max_frames, height and width must be positive"); return false; }
+    if (H % 16 || W % 16) { set_error("caddy_lpips: LPIPS (VGG16) needs height and width multiples of 16 (four 2x2 max-pools)"); return false; }
+    return true;
+}
+static caddy_ctx* make_lpips_ctx(int max_frames, int H, int W, void* ws, size_t act_cap) {
+    caddy_ctx* c = new caddy_ctx();
+    c->metrics_only = true; c->dry = ws == nullptr;
+    c->cfg.batch = max_frames; c->cfg.seq_len = 1; c->cfg.height = H; c->cfg.width = W; c->cfg.perceptual = 1;
+    c->persist.base = (char*)ws; c->persist.cap = (size_t)-1;
+    vgg_build(c, VGG_KIND_LPIPS);
+    c->sat_flag = (unsigned*)c->persist.alloc(sizeof(unsigned) * 2 * CADDY_N_FLAGS);
+    c->fm_out = (double*)c->persist.alloc(sizeof(double) * FM_SLOTS * (size_t)max_frames);      // (FM_SLOTS >= LPIPS_ROWS rows: caddy_platform_positions keeps working on it)
+    const size_t pbytes = (c->persist.high + 4095) & ~(size_t)4095;
+    c->act.base = (char*)ws + pbytes; c->act.cap = act_cap; c->grad_delta = 0;
+    c->act.reset();
+    return c;
+}
+static void lpips_sizes(int max_frames, int H, int W, size_t* persist, size_t* act) {
+    caddy_ctx* c = make_lpips_ctx(max_frames, H, W, nullptr, (size_t)1 << 50);
+    vgg_lpips_chunk(c, nullptr, nullptr, max_frames, 1.f, nullptr, max_frames);
+    *persist = (c->persist.high + 4095) & ~(size_t)4095;
+    *act = ((c->act.high + 4095) & ~(size_t)4095) + 4096;
+    delete c;
+}
+
 extern "C" {
+size_t caddy_lpips_workspace_bytes(int max_frames, int height, int width) {
+    if (!lpips_args_ok(max_frames, height, width)) return 0;
+    size_t p, a; lpips_sizes(max_frames, height, width, &p, &a);
+    return p + a + 4096;
+}
+caddy_ctx* caddy_lpips_ctx_create(int max_frames, int height, int width, void* workspace, size_t bytes) {
+    if (!lpips_args_ok(max_frames, height, width)) return nullptr;
+    if (!workspace) { set_error("null buffer"); return nullptr; }
+    if ((uintptr_t)workspace & 255) { set_error("the workspace must be 256-byte aligned"); return nullptr; }
+    size_t p, a; lpips_sizes(max_frames, height, width, &p, &a);
+    if (bytes < p + a) { set_error("workspace too small (see caddy_lpips_workspace_bytes)"); return nullptr; }
+    caddy_ctx* c = make_lpips_ctx(max_frames, height, width, workspace, a);
+    hipMemset(c->sat_flag, 0, sizeof(unsigned) * 2 * CADDY_N_FLAGS);
+    if (const char* e = getenv("CADDY_VGG_S16")) c->vgg_s16 = atoi(e) != 0;
+    if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) c->vgg_precision = c->vgg_precision_bwd = PREC_FP32;
+    return c;
+}
+int caddy_lpips_param_count(void) { return lpips_param_count(); }
+int caddy_lpips_param_info_get(int index, caddy_param_info* out) { return lpips_param_info(index, out); }
+long caddy_lpips_param_floats(void) { return lpips_param_floats(); }
+int caddy_load_lpips(caddy_ctx* c, const float* lpips_flat) {
+    if (!c || !c->metrics_only || c->vgg.kind != VGG_KIND_LPIPS) { set_error("caddy_load_lpips needs a context from caddy_lpips_ctx_create"); return -2; }
+    c->fail = false;
+    if (!lpips_flat) { set_error("null input"); return -2; }
+    return vgg_load(c, lpips_flat);
+}
+int caddy_debug_lpips_tap_formats(caddy_ctx* c) { return (c && c->vgg.kind == VGG_KIND_LPIPS) ? (int)c->vgg.tap_s16 : -1; }
+int caddy_frame_lpips(caddy_ctx* c, const float* ref, const float* gen, int B, int T, float value_range, double* out_host) {
+    if (!c || !c->metrics_only || c->vgg.kind != VGG_KIND_LPIPS) { set_error("caddy_frame_lpips needs a context from caddy_lpips_ctx_create"); return -2; }
+    c->fail = false;
+    if (!ref || !gen || !out_host) { set_error("null input"); return -2; }
+    if (B < 1 || T < 1 || !(value_range > 0.f)) { set_error("caddy_frame_lpips: B, T and value_range must be positive"); return -2; }
+    if (!c->vgg.loaded) { set_error("caddy_frame_lpips: no LPIPS weights were loaded (caddy_load_lpips)"); return -2; }
+    const int M = c->cfg.batch;
+    const long N = (long)B * T, fr = 3L * c->cfg.height * c->cfg.width;
+    hipStream_t st = c->stream;
+    std::vector<double> tmp((size_t)LPIPS_ROWS * M);
+    c->vgg.tap_s16 = 0;
+    for (long n0 = 0; n0 < N; n0 += M) {      // chunks of max_frames frames (the arena of the VGG16 trunk)
+        const int nf = (int)std::min<long>(M, N - n0);
+        for (int attempt = 0; attempt < 2; attempt++) {
+            // f16 range guard of the split-f16 forward, as in caddy_frame_metrics: a layer that met |x| > 65504 moves to split bf16 for good and the chunk runs again
+            if (vgg_lpips_chunk(c, ref + n0 * fr, gen + n0 * fr, nf, value_range, c->fm_out, M) != 0) return finish(c);
+            unsigned v[VGG_NCONV];
+            hipMemcpyAsync(v, c->sat_flag + CADDY_VGG_FLAG0, sizeof(v), hipMemcpyDeviceToHost, st);
+            hipStreamSynchronize(st);
+            bool again = false;
+            for (int i = 0; i < VGG_NCONV; i++) if (v[i] && !c->layer_fallback[CADDY_VGG_FLAG0 + i]) { c->layer_fallback[CADDY_VGG_FLAG0 + i] = true; c->n_fallback++; again = true; }
+            if (!again) break;
+            hipMemsetAsync(c->sat_flag, 0, sizeof(unsigned) * 2 * CADDY_N_FLAGS, st);
+        }
+        hipMemcpyAsync(tmp.data(), c->fm_out, sizeof(double) * LPIPS_ROWS * M, hipMemcpyDeviceToHost, st);
+        hipStreamSynchronize(st);
+        for (int s = 0; s < LPIPS_ROWS; s++)
+            for (int j = 0; j < nf; j++) out_host[s * N + n0 + j] = tmp[(size_t)s * M + j];
+    }
+    return finish(c);
+}
 size_t caddy_metrics_workspace_bytes(int max_frames, int height, int width, int vgg) {
     if (!metrics_args_ok(max_frames, height, width, vgg)) return 0;
     size_t p, a; metrics_sizes(max_frames, height, width, vgg, &p, &a);
@@ -1617,7 +1704,7 @@ caddy_ctx* caddy_metrics_ctx_create(int max_frames, int height, int width, int v
     return c;
 }
 int caddy_frame_metrics(caddy_ctx* c, const float* ref, const float* gen, int B, int T, float value_range, int want_vgg, double* out_host) {
-    if (!c || !c->metrics_only) { set_error("caddy_frame_metrics needs a context from caddy_metrics_ctx_create"); return -2; }
+    if (!c || !c->metrics_only || c->vgg.kind != VGG_KIND_VGG19) { set_error("caddy_frame_metrics needs a context from caddy_metrics_ctx_create"); return -2; }
     c->fail = false;
     if (!ref || !gen || !out_host) { set_error("null input"); return -2; }
     if (B < 1 || T < 1 || !(value_range > 0.f)) { set_error("caddy_frame_metrics: B, T and value_range must be positive"); return -2; }
@@ -1806,6 +1893,7 @@ long caddy_vgg_param_floats(void) { return vgg_param_floats(); }
 int caddy_load_vgg(caddy_ctx* c, const float* vgg_flat) {
     c->fail = false;
     if (!vgg_flat) { set_error("null input"); return -2; }
+    if (c->vgg.kind != VGG_KIND_VGG19) { set_error("caddy_load_vgg: the context is an LPIPS context (use caddy_load_lpips)"); return -2; }
     return vgg_load(c, vgg_flat);
 }
 int caddy_set_perceptual_prefetch(caddy_ctx* c, int on) { c->perc_prefetch = on != 0; return 0; }

@@ -16,6 +16,7 @@
 // The kernels here are the 2x2 max-pool (forward; backward fused with the ReLU mask of the layer below) and the feature L1.
 #include "net.h"
 #include "perceptual.h"
+#include "lpips.h"
 #include <cstdio>
 #include <cstring>
 
@@ -24,10 +25,14 @@
 namespace {
 
 // torchvision vgg19().features: (index, Cin, Cout) of the 13 convolutions the reference evaluates; pool_before: MaxPool2d(2,2) on the input
-struct VggSpec { int idx, cin, cout, pool_before, tap; };
-const VggSpec VGG[VGG_NCONV] = {
+const VggSpec VGG19_SPEC[VGG_NCONV] = {
     {0, 3, 64, 0, 0}, {2, 64, 64, 0, -1}, {5, 64, 128, 1, 1}, {7, 128, 128, 0, -1}, {10, 128, 256, 1, 2}, {12, 256, 256, 0, -1}, {14, 256, 256, 0, -1},
     {16, 256, 256, 0, -1}, {19, 256, 512, 1, 3}, {21, 512, 512, 0, -1}, {23, 512, 512, 0, -1}, {25, 512, 512, 0, -1}, {28, 512, 512, 1, 4}};
+// torchvision vgg16().features up to relu5_3 (the slices of lpips.LPIPS(net='vgg')): every tap is the last conv in front of a pool (or the last conv)
+const VggSpec LPIPS_SPEC[VGG_NCONV] = {
+    {0, 3, 64, 0, -1}, {2, 64, 64, 0, 0}, {5, 64, 128, 1, -1}, {7, 128, 128, 0, 1}, {10, 128, 256, 1, -1}, {12, 256, 256, 0, -1}, {14, 256, 256, 0, 2},
+    {17, 256, 512, 1, -1}, {19, 512, 512, 0, -1}, {21, 512, 512, 0, 3}, {24, 512, 512, 1, -1}, {26, 512, 512, 0, -1}, {28, 512, 512, 0, 4}};
+const int LPIPS_C[5] = {64, 128, 256, 512, 512};
 
 // MaxPool2d(2, 2) on dense NHWC maps; odd sizes floor like torch (the last row / column is not covered by any window)
 __global__ __launch_bounds__(256) void k_maxpool2(const float* in, float* out, long n_out4, int Hi, int Wi, int C4) {
@@ -266,53 +271,73 @@ void launch_maxpool_bwd(hipStream_t st, const T4& pre, const float* gp, bool gz_
 }
 }  // namespace
 
-int vgg_param_count() { return 2 * VGG_NCONV; }
-long vgg_param_floats() {
+const VggSpec* vgg_spec_table(int kind) { return kind == VGG_KIND_LPIPS ? LPIPS_SPEC : VGG19_SPEC; }
+static long spec_param_floats(const VggSpec* VS) {
     long n = 0;
-    for (int i = 0; i < VGG_NCONV; i++) n += (long)VGG[i].cout * VGG[i].cin * 9 + round_up(VGG[i].cout, 4);
+    for (int i = 0; i < VGG_NCONV; i++) n += (long)VS[i].cout * VS[i].cin * 9 + round_up(VS[i].cout, 4);
     return n;
 }
-int vgg_param_info(int index, caddy_param_info* out) {
+static int spec_param_info(const VggSpec* VS, int index, caddy_param_info* out) {
     if (index < 0 || index >= 2 * VGG_NCONV) return -1;
     long off = 0;
     for (int i = 0; i < VGG_NCONV; i++) {
-        const long nw = (long)VGG[i].cout * VGG[i].cin * 9;
+        const long nw = (long)VS[i].cout * VS[i].cin * 9;
         if (index == 2 * i || index == 2 * i + 1) {
             memset(out, 0, sizeof(*out));
             const bool w = index == 2 * i;
-            snprintf(out->name, sizeof(out->name), "features.%d.%s", VGG[i].idx, w ? "weight" : "bias");
+            snprintf(out->name, sizeof(out->name), "features.%d.%s", VS[i].idx, w ? "weight" : "bias");
             out->offset = w ? off : off + nw; out->kind = 3;
-            if (w) { out->ndim = 4; out->shape[0] = VGG[i].cout; out->shape[1] = VGG[i].cin; out->shape[2] = 3; out->shape[3] = 3; }
-            else { out->ndim = 1; out->shape[0] = VGG[i].cout; out->shape[1] = out->shape[2] = out->shape[3] = 1; }
+            if (w) { out->ndim = 4; out->shape[0] = VS[i].cout; out->shape[1] = VS[i].cin; out->shape[2] = 3; out->shape[3] = 3; }
+            else { out->ndim = 1; out->shape[0] = VS[i].cout; out->shape[1] = out->shape[2] = out->shape[3] = 1; }
             return 0;
         }
-        off += nw + round_up(VGG[i].cout, 4);
+        off += nw + round_up(VS[i].cout, 4);
     }
     return -1;
 }
+int vgg_param_count() { return 2 * VGG_NCONV; }
+long vgg_param_floats() { return spec_param_floats(VGG19_SPEC); }
+int vgg_param_info(int index, caddy_param_info* out) { return spec_param_info(VGG19_SPEC, index, out); }
+// the LPIPS network (evaluation/metrics/lpips.py:14): the 13 convolutions of its VGG16 trunk under torchvision's names, then the five 1x1 "lin" layers (1, C_l, 1, 1)
+int lpips_param_count() { return 2 * VGG_NCONV + 5; }
+long lpips_param_floats() { long n = spec_param_floats(LPIPS_SPEC); for (int l = 0; l < 5; l++) n += LPIPS_C[l]; return n; }
+int lpips_param_info(int index, caddy_param_info* out) {
+    if (index < 2 * VGG_NCONV) return spec_param_info(LPIPS_SPEC, index, out);
+    const int l = index - 2 * VGG_NCONV;
+    if (l >= 5) return -1;
+    long off = spec_param_floats(LPIPS_SPEC);
+    for (int k = 0; k < l; k++) off += LPIPS_C[k];
+    memset(out, 0, sizeof(*out));
+    snprintf(out->name, sizeof(out->name), "lin%d.model.1.weight", l);
+    out->offset = off; out->kind = 3; out->ndim = 4; out->shape[0] = 1; out->shape[1] = LPIPS_C[l]; out->shape[2] = out->shape[3] = 1;
+    return 0;
+}
 
 // persistent packed weights (forward + dgrad form) and biases: carved out of the caller's workspace when caddy_config.perceptual != 0
-void vgg_build(caddy_ctx* c) {
+void vgg_build(caddy_ctx* c, int kind) {
     VggState& V = c->vgg;
     V.enabled = true; V.loaded = false;
+    V.kind = kind; V.spec = vgg_spec_table(kind);
+    const VggSpec* VS = V.spec;
     for (int i = 0; i < VGG_NCONV; i++) {
         VggLayer& L = V.conv[i];
         PackDesc& d = L.pd;
         d = PackDesc{};
-        d.nw = 1; d.Co_each = VGG[i].cout; d.Cin = VGG[i].cin; d.KS = 3; d.nseg = 1;
-        d.seg_off[0] = 0; d.seg_C[0] = VGG[i].cin; d.seg_Cpad[0] = round_up(VGG[i].cin, CONV_BK);
-        d.Cout = VGG[i].cout; d.Cout_pad = round_up(d.Cout, conv_pick_bn(d.Cout)); d.Ktot = d.seg_Cpad[0];
+        d.nw = 1; d.Co_each = VS[i].cout; d.Cin = VS[i].cin; d.KS = 3; d.nseg = 1;
+        d.seg_off[0] = 0; d.seg_C[0] = VS[i].cin; d.seg_Cpad[0] = round_up(VS[i].cin, CONV_BK);
+        d.Cout = VS[i].cout; d.Cout_pad = round_up(d.Cout, conv_pick_bn(d.Cout)); d.Ktot = d.seg_Cpad[0];
         L.wp = (float*)c->persist.alloc((size_t)9 * d.Cout_pad * d.Ktot * 4);
         L.kd = round_up(d.Cout, CONV_BK);
-        L.cd_pad = round_up(VGG[i].cin, conv_pick_bn(VGG[i].cin));
+        L.cd_pad = round_up(VS[i].cin, conv_pick_bn(VS[i].cin));
         L.wpd = (float*)c->persist.alloc((size_t)9 * L.cd_pad * L.kd * 4);
         L.bias = (float*)c->persist.alloc((size_t)round_up(d.Cout, 4) * 4);
         for (int pl = 0; pl < 2; pl++) {
             L.wq[pl] = c->persist.alloc(hx_weight_bytes(d, -1, round_up(d.Cout, hx_pick_bn(d.Cout)), 2 - pl));
-            L.wqd[pl] = VGG[i].cin >= 32 ? c->persist.alloc(hx_weight_bytes(d, 0, round_up(VGG[i].cin, hx_pick_bn(VGG[i].cin)), 2 - pl)) : nullptr;
+            L.wqd[pl] = VS[i].cin >= 32 ? c->persist.alloc(hx_weight_bytes(d, 0, round_up(VS[i].cin, hx_pick_bn(VS[i].cin)), 2 - pl)) : nullptr;
         }
         L.wq[2] = c->persist.alloc(hx_weight_bytes(d, -1, round_up(d.Cout, hx_pick_bn(d.Cout)), 2));
     }
+    if (kind == VGG_KIND_LPIPS) for (int l = 0; l < 5; l++) V.lin[l] = (float*)c->persist.alloc((size_t)LPIPS_C[l] * 4);
 }
 
 // caddy_load_vgg: `flat` = device buffer laid out per vgg_param_info (torchvision names features.{idx}.weight / .bias, OIHW fp32)
@@ -320,21 +345,26 @@ int vgg_load(caddy_ctx* c, const float* flat) {
     VggState& V = c->vgg;
     if (!V.enabled) { set_error("caddy_load_vgg: the context was created with caddy_config.perceptual = 0"); return -2; }
     bool dry = c->dry;
+    const VggSpec* VS = V.spec;
     long off = 0;
     for (int i = 0; i < VGG_NCONV; i++) {
         VggLayer& L = V.conv[i];
-        const long nw = (long)VGG[i].cout * VGG[i].cin * 9;
+        const long nw = (long)VS[i].cout * VS[i].cin * 9;
         L.pd.w[0] = flat + off;
         RUN_CK(c, pack_fwd(L.pd, L.wp, c->stream));
         RUN_CK(c, pack_dgrad(L.pd, 0, L.wpd, L.cd_pad, L.kd, c->stream));
         for (int pl = 0; pl < 2; pl++) {
             RUN_CK(c, pack_hx(L.pd, L.wq[pl], round_up(L.pd.Cout, hx_pick_bn(L.pd.Cout)), -1, pl == 0 ? PREC_F16X3 : PREC_F16X1, c->stream));
-            if (L.wqd[pl]) RUN_CK(c, pack_hx(L.pd, L.wqd[pl], round_up(VGG[i].cin, hx_pick_bn(VGG[i].cin)), 0, pl == 0 ? PREC_BF16X3 : PREC_BF16X1, c->stream));
+            if (L.wqd[pl]) RUN_CK(c, pack_hx(L.pd, L.wqd[pl], round_up(VS[i].cin, hx_pick_bn(VS[i].cin)), 0, pl == 0 ? PREC_BF16X3 : PREC_BF16X1, c->stream));
         }
         RUN_CK(c, pack_hx(L.pd, L.wq[2], round_up(L.pd.Cout, hx_pick_bn(L.pd.Cout)), -1, PREC_BF16X3, c->stream));
-        if (!dry) hipLaunchKernelGGL(k_copy_f, dim3(1), dim3(256), 0, c->stream, flat + off + nw, L.bias, (long)VGG[i].cout);
+        if (!dry) hipLaunchKernelGGL(k_copy_f, dim3(1), dim3(256), 0, c->stream, flat + off + nw, L.bias, (long)VS[i].cout);
         L.pd.w[0] = nullptr;      // the caller's buffer is not referenced after this call
-        off += nw + round_up(VGG[i].cout, 4);
+        off += nw + round_up(VS[i].cout, 4);
+    }
+    if (V.kind == VGG_KIND_LPIPS) for (int l = 0; l < 5; l++) {
+        if (!dry) hipLaunchKernelGGL(k_copy_f, dim3(1), dim3(256), 0, c->stream, flat + off, V.lin[l], (long)LPIPS_C[l]);
+        off += LPIPS_C[l];
     }
     V.loaded = true;
     return c->fail ? -1 : 0;
@@ -355,7 +385,8 @@ int conv_call(caddy_ctx* c, const ConvArgs& a, double flops, int kind) {
 bool vgg_use_s16(const caddy_ctx* c) { return c->vgg_s16 && c->vgg_precision == PREC_F16X3 && c->vgg_precision_bwd == PREC_BF16X3; }
 // is conv i's launch on an N x H x W input one of the k_conv_hx variants that read / write S16 tensors?
 bool vgg_io_ok(const caddy_ctx* c, int i, int N, int H, int W) {
-    return vgg_use_s16(c) && VGG[i].cin >= 32 && !c->layer_fallback[CADDY_VGG_FLAG0 + i] && conv_hx_s16_ok(N, H, W, VGG[i].cout);      // (a layer on the split-bf16 fallback exchanges fp32 tensors)
+    const VggSpec* VS = c->vgg.spec;
+    return vgg_use_s16(c) && VS[i].cin >= 32 && !c->layer_fallback[CADDY_VGG_FLAG0 + i] && conv_hx_s16_ok(N, H, W, VS[i].cout);      // (a layer on the split-bf16 fallback exchanges fp32 tensors)
 }
 
 // 13 x (conv3x3 + bias + ReLU) with the 2x2 max-pools; taps[] (if given) receive the five tapped feature maps in place.
@@ -365,12 +396,13 @@ bool vgg_io_ok(const caddy_ctx* c, int i, int N, int H, int W) {
 void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool keep_all) {
     bool dry = c->dry;
     VggState& V = c->vgg;
+    const VggSpec* VS = V.spec;
     T4 x = img;
     T4 pooled{};                                              // output of a max-pool fused into the previous conv's epilogue
     bool have_pooled = false;
     for (int i = 0; i < VGG_NCONV; i++) {
         VggLayer& L = V.conv[i];
-        if (VGG[i].pool_before) {
+        if (VS[i].pool_before) {
             if (have_pooled) { B.p[i] = pooled; x = pooled; have_pooled = false; }
             else {
                 T4 p = valloc(c, x.N, x.H / 2, x.W / 2, x.C);
@@ -380,7 +412,7 @@ void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool ke
                 B.p[i] = p; x = p;
             }
         }
-        T4 out = (taps && VGG[i].tap >= 0) ? taps[VGG[i].tap] : valloc(c, x.N, x.H, x.W, VGG[i].cout);
+        T4 out = (taps && VS[i].tap >= 0) ? taps[VS[i].tap] : valloc(c, x.N, x.H, x.W, VS[i].cout);
         out.fmt = 0;
         ConvArgs a{};
         a.src[0] = ConvSrc{x.d, x.sn, x.ld, x.C, round_up(x.C, CONV_BK), 0};
@@ -393,16 +425,16 @@ void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool ke
         if (a.precision != PREC_FP32) a.wq = L.wq[a.precision == PREC_F16X1 ? 1 : (a.precision == PREC_BF16X3 ? 2 : 0)];
         a.sat_flag = c->sat_flag + CADDY_VGG_FLAG0 + i;
         const bool io_here = vgg_io_ok(c, i, x.N, x.H, x.W);
-        const bool pool_next = i + 1 < VGG_NCONV && VGG[i + 1].pool_before;
+        const bool pool_next = i + 1 < VGG_NCONV && VS[i + 1].pool_before;
         a.in_s16 = x.fmt;
         if (x.fmt && !io_here) { c->fail = true; set_error("internal: S16 input for a VGG19 launch that cannot read it"); }
         // MaxPool2d(2, 2) in front of the next conv: written by THIS conv's epilogue on the split-operand kernel (the window's four pixels sit in
         // one lane) -- no separate pass over the full-resolution map; a branch that is never back-propagated (keep_all = false: the ground truth)
-        // does not even store the full-resolution map of such a layer (it is no tap: the taps are the first convs AFTER a pool)
-        if (pool_next && a.wq && a.precision == PREC_F16X3 && VGG[i].cin >= 32 && conv_hx_pool_ok(x.N, x.H, x.W, VGG[i].cout)) {
-            pooled = valloc(c, x.N, x.H / 2, x.W / 2, VGG[i].cout);
+        // does not even store the full-resolution map of such a layer unless it is a tap (VGG19: never, its taps are the first convs AFTER a pool; the VGG16 trunk of LPIPS: always)
+        if (pool_next && a.wq && a.precision == PREC_F16X3 && VS[i].cin >= 32 && conv_hx_pool_ok(x.N, x.H, x.W, VS[i].cout)) {
+            pooled = valloc(c, x.N, x.H / 2, x.W / 2, VS[i].cout);
             a.pool_out = pooled.d; a.pool_sn = pooled.sn; a.pool_ld = pooled.ld;
-            a.skip_out = (!keep_all && VGG[i].tap < 0) ? 1 : 0;
+            a.skip_out = (!keep_all && VS[i].tap < 0) ? 1 : 0;
             have_pooled = true;
             // the pooled map as S16 when its consumer (conv i + 1 on the pooled geometry) reads S16; the full-resolution map (read by the max-pool backward only) in the same format
             if (io_here && vgg_io_ok(c, i + 1, x.N, x.H / 2, x.W / 2)) { a.pool_s16 = 1; pooled.fmt = 1; if (!a.skip_out) { a.out_s16 = 1; out.fmt = 1; } }
@@ -411,7 +443,7 @@ void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool ke
             if (i + 1 == VGG_NCONV || vgg_io_ok(c, i + 1, x.N, x.H, x.W)) { a.out_s16 = 1; out.fmt = 1; }
         }
         a.sat_out_next = ((a.out_s16 || a.pool_s16) && i + 1 < VGG_NCONV) ? 1 : 0;      // a clamped OUTPUT value is the next layer's range problem (flag words are consecutive per layer)
-        if (!dry) c->ck(conv_call(c, a, 2.0 * x.N * x.H * x.W * 9.0 * VGG[i].cin * VGG[i].cout, 3), "vgg conv");
+        if (!dry) c->ck(conv_call(c, a, 2.0 * x.N * x.H * x.W * 9.0 * VS[i].cin * VS[i].cout, 3), "vgg conv");
         B.a[i] = out; x = out;
     }
 }
@@ -424,6 +456,7 @@ void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool ke
 void vgg_gt_prefetch(caddy_ctx* c, int Trec, int t_off) {
     bool dry = c->dry;
     const caddy_config& g = c->cfg;
+    const VggSpec* VS = c->vgg.spec;
     const int tc[5] = {64, 128, 256, 512, 512};
     // chunk table of this forward pass (caddy_ctx::perc_plan): the taps are laid out per chunk, whatever the loss call then does with them.  Pretraining (no BPTT chain to run
     // beside) and evaluation passes keep one chunk.
@@ -477,7 +510,7 @@ void vgg_gt_prefetch(caddy_ctx* c, int Trec, int t_off) {
             c->act.off = c->gt_scratch_off;                    // (host-side bump pointer only: the region is private to the side stream)
             Branch G{};
             vgg_forward(c, gi, G, c->gt_taps_c[k][r], false);
-            for (int i = 0; i < VGG_NCONV; i++) if (VGG[i].tap >= 0) c->gt_taps_c[k][r][VGG[i].tap].fmt = G.a[i].fmt;      // (a tapped map may be an S16 tensor)
+            for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) c->gt_taps_c[k][r][VS[i].tap].fmt = G.a[i].fmt;      // (a tapped map may be an S16 tensor)
             c->act.off = keep;
         }
     }
@@ -495,6 +528,7 @@ void vgg_gt_prefetch(caddy_ctx* c, int Trec, int t_off) {
 void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv) {
     bool dry = c->dry;
     VggState& V = c->vgg;
+    const VggSpec* VS = V.spec;
     hipStream_t st = c->stream;
     const caddy_config& g = c->cfg;
     const bool pre = c->gt_prefetched && !dry;      // the ground-truth branch already ran beside the forward pass (vgg_gt_prefetch)
@@ -550,23 +584,23 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
             }
             const size_t mark2 = c->act.off;
             vgg_forward(c, gi, G, taps, false);
-            for (int i = 0; i < VGG_NCONV; i++) if (VGG[i].tap >= 0) taps[VGG[i].tap].fmt = G.a[i].fmt;
+            for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) taps[VS[i].tap].fmt = G.a[i].fmt;
             c->act.off = mark2;                  // stream order: the temporaries of the ground-truth branch are dead before anything below overwrites them
         }
         vgg_forward(c, rec, R, nullptr, true);
         // per-level sums and weights.  w_l = lambda * (l == 0 ? 1 : 2) / 3 / numel_l   (aliasing of level 0 with the total, see the header); numel_l counts ALL B x Trec frames
         float wl[5];
         int li[5];
-        for (int i = 0; i < VGG_NCONV; i++) if (VGG[i].tap >= 0) li[VGG[i].tap] = i;
+        for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) li[VS[i].tap] = i;
         // formats of the feature gradients gz_i = d/d(pre-ReLU output of conv i), stored at the gradient mirror of a[i]: S16-bf16 when the dgrad of conv i that consumes it runs on an
         // S16-capable launch AND its producer can write it -- the point-wise producers (feature L1 seed of relu5_1, max-pool backward) always can, the dgrad of conv i + 1 when it is
         // such a launch itself
         bool io_d[VGG_NCONV], gzs[VGG_NCONV];
         for (int i = 0; i < VGG_NCONV; i++) {
-            const T4& in = VGG[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec);
-            io_d[i] = vgg_use_s16(c) && i > 0 && V.conv[i].wqd[0] != nullptr && conv_hx_s16_ok(in.N, in.H, in.W, VGG[i].cin);
+            const T4& in = VS[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec);
+            io_d[i] = vgg_use_s16(c) && i > 0 && V.conv[i].wqd[0] != nullptr && conv_hx_s16_ok(in.N, in.H, in.W, VS[i].cin);
         }
-        for (int i = 0; i < VGG_NCONV; i++) gzs[i] = io_d[i] && (i + 1 == VGG_NCONV || VGG[i + 1].pool_before || io_d[i + 1]);
+        for (int i = 0; i < VGG_NCONV; i++) gzs[i] = io_d[i] && (i + 1 == VGG_NCONV || VS[i + 1].pool_before || io_d[i + 1]);
         for (int l = 0; l < 5; l++) {
             const T4& f = R.a[li[l]];
             const double numel = (double)B * Trec * f.H * f.W * f.C;
@@ -579,23 +613,23 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
             for (int i = VGG_NCONV - 1; i >= 0; i--) {
                 VggLayer& L = V.conv[i];
                 const T4& gz = R.a[i];
-                const T4& in = VGG[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec);
+                const T4& in = VS[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec);
                 ConvArgs d{};
                 d.src[0] = ConvSrc{gz.g, gz.sn, gz.ld, L.pd.Cout, L.kd, 0};
                 d.nsrc = 1; d.N = in.N; d.H = in.H; d.W = in.W; d.KS = 3; d.wp = L.wpd; d.Ktot = L.kd;
-                d.Cout = VGG[i].cin; d.Cout_pad = L.cd_pad; d.bias = nullptr; d.act = 0; d.aux = aux;
+                d.Cout = VS[i].cin; d.Cout_pad = L.cd_pad; d.bias = nullptr; d.act = 0; d.aux = aux;
                 d.precision = c->vgg_precision_bwd == PREC_BF16X1 ? PREC_BF16X1 : (c->vgg_precision_bwd == PREC_FP32 ? PREC_FP32 : PREC_BF16X3);
                 if (d.precision != PREC_FP32 && L.wqd[0]) d.wq = L.wqd[d.precision == PREC_BF16X1 ? 1 : 0];
                 d.out = in.g; d.out_sn = in.sn; d.out_ld = in.ld;
                 d.in_s16 = gzs[i] ? 1 : 0;
                 if (i == 0) d.accumulate = whole ? 1 : 0;                     // whole batch: += into d(rec_r), next to the L1 seed; a chunk: assigned to the gathered copy, added below
-                else if (!VGG[i].pool_before) {                               // direct input a[i-1]: ReLU mask (+ L1 seed when a[i-1] is tapped) in the epilogue; the output IS gz_{i-1}
+                else if (!VS[i].pool_before) {                               // direct input a[i-1]: ReLU mask (+ L1 seed when a[i-1] is tapped) in the epilogue; the output IS gz_{i-1}
                     d.mask = in.d; d.mask_s16 = in.fmt;
-                    if (VGG[i - 1].tap >= 0) { const T4& tp = taps[VGG[i - 1].tap]; d.seed_ref = tp.d; d.seed_w = wl[VGG[i - 1].tap]; d.seed_s16 = tp.fmt; }
+                    if (VS[i - 1].tap >= 0) { const T4& tp = taps[VS[i - 1].tap]; d.seed_ref = tp.d; d.seed_w = wl[VS[i - 1].tap]; d.seed_s16 = tp.fmt; }
                     d.out_s16 = gzs[i - 1] ? 1 : 0;
                 }
-                if (!dry) c->ck(conv_call(c, d, 2.0 * in.N * in.H * in.W * 9.0 * VGG[i].cin * VGG[i].cout, 4), "vgg dgrad");
-                if (VGG[i].pool_before) {                                     // pooled input: route through the max-pool and the ReLU of a[i-1] (fp32 gradient of the pooled map -> gz_{i-1})
+                if (!dry) c->ck(conv_call(c, d, 2.0 * in.N * in.H * in.W * 9.0 * VS[i].cin * VS[i].cout, 4), "vgg dgrad");
+                if (VS[i].pool_before) {                                     // pooled input: route through the max-pool and the ReLU of a[i-1] (fp32 gradient of the pooled map -> gz_{i-1})
                     if (!dry) launch_maxpool_bwd(st, R.a[i - 1], (const float*)in.g, gzs[i - 1]);
                 }
             }
@@ -627,6 +661,7 @@ int vgg_eval_per_frame(caddy_ctx* c, double* out_host) {
     const int Trec = c->pretraining ? g.seq_len : g.seq_len - 1, t_off = c->pretraining ? 0 : 1;
     const T4& rec = c->frames[0];
     const int N = rec.N;
+    const VggSpec* VS = c->vgg.spec;
     hipStream_t st = c->stream;
     if (c->gt_prefetched) hipStreamWaitEvent(st, c->gt_done, 0);      // (a training-mode forward started the ground-truth branch on the side stream: its scratch lies below fwd_off, untouched here)
     c->act.off = c->fwd_off;
@@ -640,9 +675,9 @@ int vgg_eval_per_frame(caddy_ctx* c, double* out_host) {
     double* acc = c->dalloc(5 * (size_t)N);
     hipMemsetAsync(acc, 0, sizeof(double) * 5 * (size_t)N, st);
     const size_t mark2 = c->act.off;
-    { Branch G{}; vgg_forward(c, gi, G, tg, false); for (int i = 0; i < VGG_NCONV; i++) if (VGG[i].tap >= 0) tg[VGG[i].tap].fmt = G.a[i].fmt; }
+    { Branch G{}; vgg_forward(c, gi, G, tg, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tg[VS[i].tap].fmt = G.a[i].fmt; }
     c->act.off = mark2;
-    { Branch R{}; vgg_forward(c, rec, R, tr, false); for (int i = 0; i < VGG_NCONV; i++) if (VGG[i].tap >= 0) tr[VGG[i].tap].fmt = R.a[i].fmt; }
+    { Branch R{}; vgg_forward(c, rec, R, tr, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tr[VS[i].tap].fmt = R.a[i].fmt; }
     if (c->act.overflow()) { c->act.off = mark; set_error("caddy_perceptual_per_frame: workspace too small"); return -1; }
     for (int l = 0; l < 5; l++) launch_feat_l1_img(st, tr[l], tg[l], acc + (size_t)l * N);
     hipMemcpyAsync(out_host, acc, sizeof(double) * 5 * (size_t)N, hipMemcpyDeviceToHost, st);
@@ -658,6 +693,7 @@ int vgg_eval_per_frame(caddy_ctx* c, double* out_host) {
 int vgg_metric_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, float range, double* out) {
     const bool dry = c->dry;
     const int H = c->cfg.height, W = c->cfg.width;
+    const VggSpec* VS = c->vgg.spec;
     hipStream_t st = c->stream;
     const size_t mark = c->act.off;
     const int tc[5] = {64, 128, 256, 512, 512};
@@ -674,13 +710,50 @@ int vgg_metric_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, f
     for (int l = 0; l < 5; l++) { lv.off[l] = total; lv.blocks[l] = cos_blocks(tr[l]); total += (long)nf * lv.blocks[l] * 3; }
     double* part = c->dalloc((size_t)total);
     const size_t mark2 = c->act.off;
-    { Branch Rb{}; vgg_forward(c, gr, Rb, tr, false); for (int i = 0; i < VGG_NCONV; i++) if (VGG[i].tap >= 0) tr[VGG[i].tap].fmt = Rb.a[i].fmt; }
+    { Branch Rb{}; vgg_forward(c, gr, Rb, tr, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tr[VS[i].tap].fmt = Rb.a[i].fmt; }
     c->act.off = mark2;
-    { Branch Gb{}; vgg_forward(c, gg, Gb, tg, false); for (int i = 0; i < VGG_NCONV; i++) if (VGG[i].tap >= 0) tg[VGG[i].tap].fmt = Gb.a[i].fmt; }
+    { Branch Gb{}; vgg_forward(c, gg, Gb, tg, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tg[VS[i].tap].fmt = Gb.a[i].fmt; }
     if (c->act.overflow()) { c->act.off = mark; set_error("caddy_frame_metrics: workspace too small"); return -1; }
     if (!dry) {
         for (int l = 0; l < 5; l++) launch_feat_cos_img(st, tr[l], tg[l], part + lv.off[l]);
         hipLaunchKernelGGL(k_feat_cos_finalize, dim3((nf + 63) / 64), dim3(64), 0, st, (const double*)part, lv, nf, out);
+    }
+    c->act.off = mark;
+    return c->fail ? -1 : 0;
+}
+
+// Dataset evaluation (evaluation/metrics/lpips.py:14,33: lpips.LPIPS(net='vgg') per observation, on a context from caddy_lpips_ctx_create): LPIPS of frames [0, nf) of `ref` / `gen`
+// ((nf, 3, H, W) fp32 in [0, range]).  out[0 * ldo + n] = the distance, out[(1 + l) * ldo + n] = its level-l term.  The walk of vgg_metric_chunk with the VGG16 trunk; the head is
+// lpips.hip.  With c->dry nothing is launched (workspace sizing).
+int vgg_lpips_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, float range, double* out, int ldo) {
+    const bool dry = c->dry;
+    const int H = c->cfg.height, W = c->cfg.width;
+    const VggSpec* VS = c->vgg.spec;
+    hipStream_t st = c->stream;
+    const size_t mark = c->act.off;
+    T4 gr = valloc(c, nf, H, W, 3), gg = valloc(c, nf, H, W, 3);
+    const long npix = (long)nf * H * W;
+    if (!dry) {
+        lpips_stage_launch(st, ref, gr.d, npix, (long)H * W, range);
+        lpips_stage_launch(st, gen, gg.d, npix, (long)H * W, range);
+    }
+    T4 tr[5], tg[5];
+    { int h = H, w = W; for (int l = 0; l < 5; l++) { tr[l] = valloc(c, nf, h, w, LPIPS_C[l]); tg[l] = valloc(c, nf, h, w, LPIPS_C[l]); h /= 2; w /= 2; } }
+    LpipsLevels lv{};
+    long total = 0;
+    for (int l = 0; l < 5; l++) { lv.off[l] = total; lv.blocks[l] = lpips_blocks(tr[l].H * tr[l].W); lv.inv_px[l] = 1.0 / ((double)tr[l].H * tr[l].W); total += (long)nf * lv.blocks[l]; }
+    double* part = c->dalloc((size_t)total);
+    const size_t mark2 = c->act.off;
+    { Branch Rb{}; vgg_forward(c, gr, Rb, tr, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tr[VS[i].tap].fmt = Rb.a[i].fmt; }
+    c->act.off = mark2;
+    { Branch Gb{}; vgg_forward(c, gg, Gb, tg, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tg[VS[i].tap].fmt = Gb.a[i].fmt; }
+    if (c->act.overflow()) { c->act.off = mark; set_error("caddy_frame_lpips: workspace too small"); return -1; }
+    if (!dry) {
+        for (int l = 0; l < 5; l++) {
+            if (tr[l].fmt && tg[l].fmt) c->vgg.tap_s16 |= 1u << l;
+            c->ck(lpips_head_launch(st, tr[l].d, tr[l].fmt != 0, tg[l].d, tg[l].fmt != 0, c->vgg.lin[l], nf, tr[l].H * tr[l].W, tr[l].C, lv.blocks[l], part + lv.off[l]), "lpips head");
+        }
+        lpips_finalize_launch(st, part, lv, nf, out, ldo);
     }
     c->act.off = mark;
     return c->fail ? -1 : 0;

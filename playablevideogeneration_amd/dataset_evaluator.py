@@ -3,8 +3,9 @@ seam of evaluate_dataset.py (factory `evaluator(config, logger, reference_datase
 
 Per frame, on the device: mse, motion_masked_mse, psnr, ssim and -- when VGG19 weights are configured (`evaluation.vgg19_weights` or
 `evaluation.vgg19_from_torchvision`, the loader of Trainer._find_vgg_weights) -- vgg_sim, all from one fused HIP pass (metrics.FrameMetrics).  The
-keys are those of compute_positional_statistics: {m}/avg, {m}/var, {m}/{i}, {m}/{i}/var.  LPIPS, FID, FVD, IS and the plots need pretrained networks
-that are not available and are not computed.  The per-dataset evaluators that add the detection and action metrics of Breakout and BAIR are
+keys are those of compute_positional_statistics: {m}/avg, {m}/var, {m}/{i}, {m}/{i}/var.  With LPIPS weights (`evaluation.lpips_weights`, or
+`evaluation.lpips_vgg16_weights` + `evaluation.lpips_linear_weights`: metrics.find_lpips_weights) `lpips` is added (evaluation/metrics/lpips.py:14,33, on the
+HIP path: metrics.LPIPS); without them the keys are unchanged.  FID, FVD, IS and the plots need further pretrained networks and are not computed.  The per-dataset evaluators that add the detection and action metrics of Breakout and BAIR are
 dataset_evaluator_breakout and dataset_evaluator_bair (ActionSpaceEvaluator below).
 """
 from typing import Dict
@@ -38,7 +39,12 @@ class DatasetEvaluator:
         self.vgg_state = Trainer._find_vgg_weights(config["evaluation"])
         if self.vgg_state is None:
             self.logger.print("- vgg_sim skipped: no VGG19 weights configured (evaluation.vgg19_weights / evaluation.vgg19_from_torchvision)")
+        self.lpips_state = M.find_lpips_weights(config["evaluation"])
+        if self.lpips_state is None:
+            self.logger.print("- lpips skipped: no LPIPS weights configured (evaluation.lpips_weights, or evaluation.lpips_vgg16_weights + evaluation.lpips_linear_weights)")
         self.logger.print(self.NOT_COMPUTED)
+        if self.lpips_state is not None:
+            self.logger.print("- lpips is computed (LPIPS weights configured): the line above applies to it no longer")
 
     @staticmethod
     def check_range(values: Dict[str, torch.Tensor], which: str):
@@ -61,8 +67,18 @@ class DatasetEvaluator:
             results[f"{prefix}/{idx}/var"] = current_variance
         return results
 
+    def frame_values(self, reference_observations: torch.Tensor, generated_observations: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """the fused pass's slots, plus `lpips` when LPIPS weights are configured"""
+        values = M.frame_metrics(reference_observations, generated_observations, 1.0, self.vgg_state)
+        if self.lpips_state is not None:
+            values["lpips"] = M.lpips(reference_observations, generated_observations, self.lpips_state, 1.0)
+        return values
+
+    def metric_names(self, names):
+        return [m for m in names if m != "vgg_sim" or self.vgg_state is not None] + (["lpips"] if self.lpips_state is not None else [])
+
     def compute_metrics(self) -> Dict:
-        names = [m for m in METRICS if m != "vgg_sim" or self.vgg_state is not None]
+        names = self.metric_names(METRICS)
         acc = {m: [] for m in names}
         batches = len(self.reference_dataloader)
         with torch.no_grad():
@@ -70,7 +86,7 @@ class DatasetEvaluator:
                 self.logger.print(f"- Computing metrics for batch [{idx}/{batches}]")
                 reference_observations = reference_batch.to_tuple(cuda=False)[0]
                 generated_observations = generated_batch.to_tuple(cuda=False)[0]
-                values = M.frame_metrics(reference_observations, generated_observations, 1.0, self.vgg_state)
+                values = self.frame_values(reference_observations, generated_observations)
                 self.check_range(values, "ref")
                 self.check_range(values, "gen")
                 for m in names:
@@ -83,7 +99,7 @@ class DatasetEvaluator:
 
 class ActionSpaceEvaluator(DatasetEvaluator):
     """The loop of the reference's per-dataset evaluators (evaluation/dataset_evaluator_breakout.py, dataset_evaluator_bair.py): per frame mse, psnr,
-    ssim (and vgg_sim with VGG19 weights; no motion_masked_mse, as there), plus the action variance and action accuracy of the inferred actions of the
+    ssim (and vgg_sim with VGG19 weights, lpips with LPIPS weights; no motion_masked_mse, as there), plus the action variance and action accuracy of the inferred actions of the
     generated sequences against the movement that follows each of them in the reference sequences.  Subclasses say how a movement is measured
     (`movements`) and may add detections (`detect`, `detection_results`)."""
     NOT_COMPUTED = "- lpips, fid, fvd and the density plots are not computed: they need pretrained networks that are not available"
@@ -119,7 +135,7 @@ class ActionSpaceEvaluator(DatasetEvaluator):
 
     def compute_metrics(self) -> Dict:
         from . import action_metrics as A
-        names = [m for m in self.FRAME_METRICS if m != "vgg_sim" or self.vgg_state is not None]
+        names = self.metric_names(self.FRAME_METRICS)
         acc = {m: [] for m in names}
         detections, actions, movements = {}, [], []
         device = M.device()
@@ -129,7 +145,7 @@ class ActionSpaceEvaluator(DatasetEvaluator):
                 self.logger.print(f"- Computing metrics for batch [{idx}/{batches}]")
                 reference_observations = reference_batch.to_tuple(cuda=False)[0].to(device)
                 generated_observations = generated_batch.to_tuple(cuda=False)[0].to(device)
-                values = M.frame_metrics(reference_observations, generated_observations, 1.0, self.vgg_state)
+                values = self.frame_values(reference_observations, generated_observations)
                 self.check_range(values, "ref")
                 self.check_range(values, "gen")
                 for m in names:

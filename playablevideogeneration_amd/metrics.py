@@ -6,12 +6,16 @@ Inputs are (bs, observations_count, channels, height, width) tensors in the same
     motion_masked_mse           evaluation/metrics/motion_masked_mse.py:16-28 + motion_mask.py:14-37    > the fused HIP pass of csrc/frame_metrics.hip
     vgg_cosine_similarity       evaluation/metrics/vgg_cosine_similarity.py:22-57 (VGG19 relu1_1..5_1)  /  (+ the VGG19 kernels of csrc/perceptual.hip)
     breakout_platform_positions evaluation/metrics/breakout_platform_position.py                       -- the row scan of csrc/detection.hip
+    lpips                       evaluation/metrics/lpips.py:14,33 (lpips.LPIPS(net='vgg'))              -- VGG16 to relu5_3 on the VGG kernels of csrc/perceptual.hip
+                                                                                                          + the normalise / weight / average head of csrc/lpips.hip
 
 The HIP-backed metrics run on a metrics context of libcaddy_hip.so (caddy_metrics_ctx_create), cached per frame geometry; there is no torch fallback.
 `set_library` points them at another build of the same kernels (the tests' host simulator).
-(FID / FVD / LPIPS and the Tennis detector depend on pretrained networks and stay out of scope.)"""
+LPIPS needs its weights from the caller (a torchvision vgg16 state dict plus the package's five `lin` tensors, see lpips_state): nothing is downloaded.
+(FID / FVD / IS and the Tennis detector depend on further pretrained networks and stay out of scope.)"""
 import ctypes as C
-from typing import Dict
+import re
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -39,6 +43,7 @@ def set_library(lib) -> None:
     global _default_lib
     _default_lib = lib
     _contexts.clear()
+    _lpips_contexts.clear()
 
 
 def _bind(lib):
@@ -51,6 +56,15 @@ def _bind(lib):
         lib.caddy_metrics_ctx_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         lib.caddy_frame_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]
         lib.caddy_platform_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p]
+        lib.caddy_lpips_workspace_bytes.restype = C.c_size_t
+        lib.caddy_lpips_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.caddy_lpips_ctx_create.restype = C.c_void_p
+        lib.caddy_lpips_ctx_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        lib.caddy_lpips_param_floats.restype = C.c_long
+        lib.caddy_lpips_param_info_get.argtypes = [C.c_int, C.c_void_p]
+        lib.caddy_load_lpips.argtypes = [C.c_void_p, C.c_void_p]
+        lib.caddy_frame_lpips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
+        lib.caddy_debug_lpips_tap_formats.argtypes = [C.c_void_p]
         lib._caddy_metrics_bound = True
     return lib
 
@@ -216,6 +230,150 @@ def vgg_cosine_similarity(reference_observations: torch.Tensor, generated_observ
     if vgg_state_dict is None:
         raise ValueError("vgg_cosine_similarity needs VGG19 weights")
     return frame_metrics(reference_observations, generated_observations, value_range, vgg_state_dict, lib=lib)["vgg_sim"]
+
+
+# ---- LPIPS (caddy_frame_lpips) ----
+LPIPS_FRAMES_256 = 30      # frames per VGG16 chunk at 256 x 256 (scaled by the frame area), as VGG_FRAMES_256
+LPIPS_CONVS = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)      # torchvision vgg16().features indices of the trunk's convolutions
+LPIPS_LEVELS = ("relu1_2", "relu2_2", "relu3_3", "relu4_3", "relu5_3")
+LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)      # the package's scaling layer; compiled into csrc/lpips.hip
+_lpips_contexts: Dict = {}
+
+
+def lpips_state(weights: Dict[str, torch.Tensor], linear: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """The tensors of lpips.LPIPS(net='vgg') under the names of caddy_lpips_param_info_get (features.{idx}.weight / .bias, lin{l}.model.1.weight) from
+      (a) one dict with torchvision's vgg16 names (vgg16().state_dict() or .features.state_dict(): `features.{idx}.*` or `{idx}.*`) plus `lin{l}.model.1.weight`,
+      (b) the package's own state dict (`net.slice{k}.{idx}.*`, `lin{l}.model.1.weight` / `lins.{l}.model.1.weight`, optionally `scaling_layer.shift` / `.scale`,
+          which must equal the constants the kernel applies),
+      (c) the trunk in `weights` and the `lin` tensors in `linear` (the package ships only the latter and takes the trunk from torchvision).
+    A missing tensor raises CaddyError naming it."""
+    from .engine import CaddyError
+    src = dict(weights)
+    if linear is not None:
+        src.update(linear)
+    for key, want in (("scaling_layer.shift", LPIPS_SHIFT), ("scaling_layer.scale", LPIPS_SCALE)):
+        if key in src and not torch.allclose(src[key].detach().float().reshape(-1), torch.tensor(want), rtol=0, atol=1e-6):
+            raise CaddyError(f"LPIPS {key} is {src[key].reshape(-1).tolist()}, but the kernel applies {list(want)}")
+    sliced = {}
+    for k in src:
+        m = re.fullmatch(r"net\.slice\d+\.(\d+\.(?:weight|bias))", k)
+        if m:
+            sliced[m.group(1)] = k
+    out = {}
+    for idx in LPIPS_CONVS:
+        for leaf in ("weight", "bias"):
+            name = f"features.{idx}.{leaf}"
+            key = next((k for k in (name, f"{idx}.{leaf}", sliced.get(f"{idx}.{leaf}")) if k is not None and k in src), None)
+            if key is None:
+                raise CaddyError(f"LPIPS weights lack {name}")
+            out[name] = src[key]
+    for l in range(5):
+        name = f"lin{l}.model.1.weight"
+        key = next((k for k in (name, f"lins.{l}.model.1.weight") if k in src), None)
+        if key is None:
+            raise CaddyError(f"LPIPS weights lack {name}")
+        out[name] = src[key]
+    return out
+
+
+def find_lpips_weights(cfg) -> Optional[Dict[str, torch.Tensor]]:
+    """config["evaluation"] -> lpips_state(...) of `lpips_weights` (one path or dict), or of `lpips_vgg16_weights` + `lpips_linear_weights`; None when neither is configured"""
+    def load(src):
+        if isinstance(src, str):
+            sd = torch.load(src, map_location="cpu", weights_only=True)
+            return sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+        return src
+    one, trunk, lin = cfg.get("lpips_weights", None), cfg.get("lpips_vgg16_weights", None), cfg.get("lpips_linear_weights", None)
+    if one is not None:
+        return lpips_state(load(one))
+    if trunk is not None or lin is not None:
+        from .engine import CaddyError
+        if trunk is None or lin is None:
+            raise CaddyError("evaluation.lpips_vgg16_weights and evaluation.lpips_linear_weights must be given together")
+        return lpips_state(load(trunk), load(lin))
+    return None
+
+
+class LPIPS:
+    """An LPIPS context for frames of height x width (multiples of 16) with the weights of lpips_state().  Calls with more than `max_frames` frames run in chunks."""
+
+    def __init__(self, height: int, width: int, max_frames: int, lpips_weights, lib=None, device=None):
+        from . import _lib
+        from .engine import CaddyError, ParamInfo
+        self.lib = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
+        kind = getattr(self.lib, "_caddy_device_type", "cuda")
+        self.device = torch.device(device) if device is not None else torch.device(kind)
+        self.H, self.W, self.max_frames = int(height), int(width), int(max_frames)
+        self._err = lambda: self.lib.caddy_last_error().decode()
+        state = lpips_state(lpips_weights)
+        n = self.lib.caddy_lpips_workspace_bytes(self.max_frames, self.H, self.W)
+        if n == 0:
+            raise CaddyError(self._err())
+        raw = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+        self._ws = raw
+        self.ws_bytes = n
+        self.ctx = self.lib.caddy_lpips_ctx_create(self.max_frames, self.H, self.W, raw.data_ptr() + (-raw.data_ptr()) % 256, n)
+        if not self.ctx:
+            raise CaddyError(self._err())
+        info = ParamInfo()
+        flat = torch.zeros(self.lib.caddy_lpips_param_floats(), dtype=torch.float32, device=self.device)
+        for i in range(self.lib.caddy_lpips_param_count()):
+            self.lib.caddy_lpips_param_info_get(i, C.byref(info))
+            name, off, shape = info.name.decode(), info.offset, tuple(info.shape[:info.ndim])
+            t = state[name].detach().to(self.device, torch.float32)
+            if tuple(t.shape) != shape:
+                raise CaddyError(f"LPIPS {name}: shape {tuple(t.shape)}, expected {shape}")
+            flat[off:off + t.numel()] = t.reshape(-1)
+        self._stream()
+        self._check(self.lib.caddy_load_lpips(self.ctx, flat.data_ptr()))
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()
+        self.levels = None
+
+    _check = FrameMetrics._check
+    _stream = FrameMetrics._stream
+    set_vgg_precision = FrameMetrics.set_vgg_precision
+    __del__ = FrameMetrics.__del__
+
+    def tap_formats(self) -> int:
+        """bit l set: the level-l feature maps travelled as S16 tensors in some chunk of the last call (caddy_debug_lpips_tap_formats)"""
+        return int(self.lib.caddy_debug_lpips_tap_formats(self.ctx))
+
+    def __call__(self, reference_observations: torch.Tensor, generated_observations: torch.Tensor, value_range: float = 1.0, return_levels: bool = False):
+        """-> (bs, observations_count) float64 CPU tensor; with return_levels also the (5, bs, observations_count) terms of LPIPS_LEVELS (kept in self.levels either way)"""
+        r, g = reference_observations, generated_observations
+        if r.dim() != 5 or r.shape != g.shape or r.shape[2] != 3 or tuple(r.shape[3:]) != (self.H, self.W):
+            raise ValueError(f"expected two (bs, observations_count, 3, {self.H}, {self.W}) tensors, got {tuple(r.shape)} and {tuple(g.shape)}")
+        B, T = int(r.shape[0]), int(r.shape[1])
+        r = r.detach().to(self.device, torch.float32).contiguous()
+        g = g.detach().to(self.device, torch.float32).contiguous()
+        out = torch.empty(6, B, T, dtype=torch.float64)
+        self._stream()
+        self._check(self.lib.caddy_frame_lpips(self.ctx, r.data_ptr(), g.data_ptr(), B, T, float(value_range), out.data_ptr()))
+        self.levels = out[1:]
+        return (out[0], out[1:]) if return_levels else out[0]
+
+
+def _cached_lpips(observations: torch.Tensor, lpips_weights, lib) -> LPIPS:
+    """the LPIPS context of this library, device, frame geometry and weights (cached like _cached_context)"""
+    B, T, _, H, W = observations.shape
+    lib = lib if lib is not None else _default_lib
+    key = (id(lib), str(observations.device), int(H), int(W), id(lpips_weights))
+    ctx = _lpips_contexts.get(key)
+    if ctx is None:
+        want = min(int(B) * int(T), max(1, LPIPS_FRAMES_256 * 256 * 256 // (int(H) * int(W))))
+        ctx = LPIPS(H, W, min(want, 1024), lpips_weights, lib)
+        ctx._keep = lpips_weights      # (the cache key holds its id)
+        _lpips_contexts[key] = ctx
+    return ctx
+
+
+def lpips(reference_observations: torch.Tensor, generated_observations: torch.Tensor, lpips_weights, value_range: float = 1.0, lib=None,
+          return_levels: bool = False):
+    """lpips.LPIPS(net='vgg')(reference, generated, normalize=True) per observation (evaluation/metrics/lpips.py:14,33) -> (bs, observations_count) float64"""
+    if lpips_weights is None:
+        raise ValueError("lpips needs LPIPS weights (see lpips_state)")
+    return _cached_lpips(reference_observations, lpips_weights, lib)(reference_observations, generated_observations, value_range, return_levels)
 
 
 def rollout_quality(model, batch_tuple, ground_truth_observations_init: int = 1, gumbel_temperature: float = 1.0) -> dict:
