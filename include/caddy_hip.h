@@ -314,6 +314,10 @@ int caddy_debug_set_s16_grads(caddy_ctx* ctx, int on);
  * (three chunks of the full-resolution level for steps of >= 4 M reconstructed pixels, four from 1 M, else one pass; CADDY_PERC_CHUNKS changes the three, a negative value forces its magnitude).  Takes effect at the next
  * caddy_forward_full.  Same loss; gradients equal up to the summation order of the per-chunk launches. */
 int caddy_debug_set_perc_chunks(caddy_ctx* ctx, int n);
+/* tests / A-B runs: 1 (default) lets the dgrad launch above a tapped VGG19 map (relu1_1 .. relu4_1 of training/losses.py:379-491), whose epilogue loads the reconstruction's and
+ * the ground truth's features for the sign of the L1 seed, also sum |f_rec - f_gt| for the level's loss; 0 = a stand-alone pass over both maps for every level.  Same gradients
+ * bit for bit; the level sums are the same fp32 differences added in double in another order.  CADDY_PERC_FUSE_L1 sets the default of new contexts. */
+int caddy_debug_set_perc_fuse_l1(caddy_ctx* ctx, int on);
 long caddy_debug_s16_grad_count(caddy_ctx* ctx);
 int caddy_debug_set_pack_merged(caddy_ctx* ctx, int on);      /* tests: 0 = one (un)packing launch per layer and form instead of the job-table launch */
 int caddy_debug_dims(caddy_ctx* ctx, int i, int* nhwc4);

@@ -131,6 +131,10 @@ struct ConvArgs {
     // S16 OUTPUT range guard (SO launches, split f16): 1 = a value the epilogue had to clamp raises the word BEHIND *sat_flag -- the layer that will stage the tensor (VGG19 layer
     // i + 1: its fall-back makes this launch write fp32 again) -- instead of this layer's own word, whose fall-back would leave the oversized values where they are
     int sat_out_next;
+    // Feature-L1 sum of a tapped VGG19 map out of the seed epilogue (nullable; honoured only together with seed_ref, by the k_conv_hx instances conv_hx_l1_ok() accepts): the
+    // launch adds sum |mask - seed_ref| over EVERY element of the map (ReLU mask open or not; fp32 differences, summed in double) to *l1_acc -- the two maps are in registers for
+    // the sign of the seed, a stand-alone pass (perceptual.hip: k_feat_l1) would read both from HBM again.  One double atomic per workgroup; whole-K launches only.
+    double* l1_acc;
 };
 int conv_avgpool_ok(const ConvArgs& a);      // (out / out_sn / out_ld need not be set yet)
 // gates = [i | f | o | g] x C pre-activations (convolutional_lstm_cell.py:92-101): c' = sigm(f) c + sigm(i) tanh(g), h' = sigm(o) tanh(c'), hb = h' * scale + shift (the cell's
@@ -200,7 +204,8 @@ struct PackDesc;
 int conv_hx_wgrad_try(const WgradArgs& a, hipStream_t st, bool dry = false);
 int conv_hx_try(const ConvArgs& a, hipStream_t st, bool dry = false);      // dry: 1 = the launch would run here (nothing is launched)
 bool conv_hx_s16_ok(int N, int H, int W, int Cout);       // ... on a tile variant that reads / writes S16 tensors (ConvArgs.in_s16 / out_s16)?  (the same two well-filled variants)
-bool conv_hx_pool_ok(int N, int H, int W, int Cout);      // will conv_hx_try run this geometry on a tile variant with the fused max-pool epilogue?           // conv_hx.hip: 3x3 on the 16-bit MFMA with split operands (1 = handled)
+bool conv_hx_l1_ok(const ConvArgs& a);                    // will conv_fwd_launch run this masked launch (mask + seed_ref set) on a k_conv_hx instance that implements ConvArgs.l1_acc?
+bool conv_hx_pool_ok(int N, int H, int W, int Cout);    // will conv_hx_try run this geometry on a tile variant with the fused max-pool epilogue?           // conv_hx.hip: 3x3 on the 16-bit MFMA with split operands (1 = handled)
 int pack_hx(const PackDesc& d, void* wq, int rows_pad, int seg /* < 0: forward form, else dgrad form of that input segment */, int precision, hipStream_t st);
 size_t hx_weight_bytes(const PackDesc& d, int seg, int rows_pad, int planes);
 int hx_kq(const PackDesc& d, int seg);

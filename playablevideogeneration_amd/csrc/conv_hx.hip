@@ -52,16 +52,17 @@ __device__ __forceinline__ float s16_val(const float* row, int col) {
 // overlaps an epilogue).  Now: wave-uniform base pointers + 32-bit byte offsets (one add per value), the row test on the scalar unit, column tests only in workgroups that straddle
 // the image border (INTR = false), the activation as a slope select, everything a 32 x 32 block READS (mask / seed / residual / old value) requested back to back before the first
 // use, and one straight-line instance per workgroup-uniform case: MODE 0 plain assigning store, 1 + ReLU mask / L1 seed (VGG19 dgrads), 2 everything (split-K atomics / slabs,
-// residual, accumulate).  Measured: full step 141.9 -> 127.5 ms, E/R/A/D step 66.1 -> 63.1 ms (profiles/r05_experiments.md).
+// residual, accumulate), 3 = 1 + the feature-L1 sum of the tapped map (ConvArgs.l1_acc: |mask - seed_ref| of every valid element into the lane's double l1s).
+// Measured: full step 141.9 -> 127.5 ms, E/R/A/D step 66.1 -> 63.1 ms (profiles/r05_experiments.md).
 template <typename T, int TH, int TW, int BN, int WM, int WN, int EP, bool SO, bool INTR, int MODE, int TMt, int TNt>
-__device__ __forceinline__ void hx_epilogue(f32x16 (&acc)[TMt][TNt], float (&st1)[TNt], float (&st2)[TNt], unsigned& amax_o, const ConvArgs& a,
+__device__ __forceinline__ void hx_epilogue(f32x16 (&acc)[TMt][TNt], float (&st1)[TNt], float (&st2)[TNt], unsigned& amax_o, double& l1s, const ConvArgs& a,
                                             int n, int n0, int y0, int x0, int lane, int wave) {
     constexpr bool E_POOL = EP == 1 || EP == 3, E_MASK = EP == 2 || EP == 3;
     constexpr int BM = TH * TW, RW = BM / WM / TW;           // tile rows per wave
     const int wm_u = __builtin_amdgcn_readfirstlane(wave) / WN, wn = wave % WN;      // (wave-uniform copy: keeps the row arithmetic on the scalar unit)
     const int yw = y0 + wm_u * RW, xl = x0 + 4 * (lane >> 5);      // first image row of this wave's rows (uniform) / this lane's first column
     const int nx = a.W - xl;                                  // columns of this lane's row segment that lie inside the image
-    const bool masked = MODE == 1 || (MODE == 2 && E_MASK && a.mask != nullptr);
+    const bool masked = MODE == 1 || MODE == 3 || (MODE == 2 && E_MASK && a.mask != nullptr);
     const bool split = MODE == 2 && a.splitk > 1, slabs = split && a.split_stride != 0, atomics = split && !slabs;
     const bool with_res = MODE == 2 && !split && a.res != nullptr, accum = MODE == 2 && !split && a.accumulate != 0;
     char* const op = reinterpret_cast<char*>(a.out + (long)n * a.out_sn + (slabs ? (long)blockIdx.z * a.split_stride : 0L));
@@ -127,7 +128,8 @@ __device__ __forceinline__ void hx_epilogue(f32x16 (&acc)[TMt][TNt], float (&st1
                     if (with_res) v += ex[r];
                     v = v > 0.f ? v : slope * v;
                     if (masked) {
-                        if (sp != nullptr) { const float d_ = mk[r] - sd[r]; v += d_ > 0.f ? sw : (d_ < 0.f ? -sw : 0.f); }
+                        if (sp != nullptr) { const float d_ = mk[r] - sd[r]; v += d_ > 0.f ? sw : (d_ < 0.f ? -sw : 0.f);
+                                             if (MODE == 3 && HX_EOK(i, r)) l1s += (double)fabsf(d_); }      // (the guard of the store below: no padded channel -- col < Cout --, no pixel outside the image)
                         v = mk[r] > 0.f ? v : 0.f;
                     }
                     if (accum) v += ex[r];
@@ -546,6 +548,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_hx(ConvArgs a, int tiles_
 
     if (!is_bf16<T>::value && a.sat_flag != nullptr && amax > 0x477fe000u /* bits of 65504.f */) atomicOr(a.sat_flag, amax > 0x7f800000u ? 3u : 1u);      // bit 1: a NaN among them      // (rare: one atomic per saturating thread)
     unsigned amax_o = 0u;                                     // SO, split f16: the same guard on what this launch stores
+    double l1s = 0.0;                                         // ConvArgs.l1_acc: this lane's part of sum |mask - seed_ref|
     // ---- epilogue: D fragment map col = lane & 31 (output channel), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (pixel of the tile) ----
     float st1[TNt], st2[TNt];                                 // per-channel sums of the stored values (ConvArgs.stats: BatchNorm statistics of the consumer)
 #pragma unroll
@@ -555,10 +558,27 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_hx(ConvArgs a, int tiles_
         const bool interior = y0 + TH <= a.H && x0 + TW <= a.W;
         const bool general = a.splitk > 1 || a.res != nullptr || a.accumulate != 0;
         const bool masked = E_MASK && a.mask != nullptr;
-#define HX_EPI(INTR_, MODE_) hx_epilogue<T, TH, TW, BN, WM, WN, EP, SO, INTR_, MODE_>(acc, st1, st2, amax_o, a, n, n0, y0, x0, lane, wave)
-        if (interior) { if (general) HX_EPI(true, 2); else if (masked) HX_EPI(true, (E_MASK ? 1 : 0)); else HX_EPI(true, 0); }
-        else { if (general) HX_EPI(false, 2); else if (masked) HX_EPI(false, (E_MASK ? 1 : 0)); else HX_EPI(false, 0); }
+        const bool with_l1 = masked && a.seed_ref != nullptr && a.l1_acc != nullptr;      // (never together with `general`: the launcher refuses it)
+#define HX_EPI(INTR_, MODE_) hx_epilogue<T, TH, TW, BN, WM, WN, EP, SO, INTR_, MODE_>(acc, st1, st2, amax_o, l1s, a, n, n0, y0, x0, lane, wave)
+        if (interior) { if (general) HX_EPI(true, 2); else if (with_l1) HX_EPI(true, (E_MASK ? 3 : 0)); else if (masked) HX_EPI(true, (E_MASK ? 1 : 0)); else HX_EPI(true, 0); }
+        else { if (general) HX_EPI(false, 2); else if (with_l1) HX_EPI(false, (E_MASK ? 3 : 0)); else if (masked) HX_EPI(false, (E_MASK ? 1 : 0)); else HX_EPI(false, 0); }
 #undef HX_EPI
+    }
+    // ---- feature-L1 sum (ConvArgs.l1_acc): every element of the tapped map belongs to exactly one workgroup of this whole-K launch -> wave shuffle, LDS, ONE double atomic per
+    // workgroup (the tail of k_feat_l1, perceptual.hip) ----
+    if constexpr (E_MASK) {
+        if (a.l1_acc != nullptr && a.seed_ref != nullptr && a.mask != nullptr && a.splitk == 1) {      // (grid-uniform)
+            __shared__ double l1sh[WM * WN];
+            for (int o = 32; o > 0; o >>= 1) l1s += __shfl_xor(l1s, o);
+            if (lane == 0) l1sh[wave] = l1s;
+            __syncthreads();
+            if (tid == 0) {
+                double t = l1sh[0];
+#pragma unroll
+                for (int w = 1; w < WM * WN; w++) t += l1sh[w];
+                atomicAdd(a.l1_acc, t);
+            }
+        }
     }
     if (SO && !is_bf16<T>::value && a.sat_flag != nullptr && amax_o > 0x477fe000u) atomicOr(a.sat_flag + (a.sat_out_next ? 1 : 0), amax_o > 0x7f800000u ? 3u : 1u);
     // ---- BatchNorm partial sums of this tile: the two 32-lane halves of a wave hold different pixel rows of one channel, the WM waves of a column
@@ -708,6 +728,15 @@ bool conv_hx_pool_ok(int N, int H, int W, int Cout) {
 
 bool conv_hx_s16_ok(int N, int H, int W, int Cout) { return (Cout & 31) == 0 && conv_hx_pool_ok(N, H, W, Cout); }
 
+// does conv_fwd_launch hand this masked launch (the dgrad behind a tapped VGG19 map: mask + seed_ref) to conv_hx_try, whose masked instances (EP = 2 / 3: every tile variant)
+// all sum ConvArgs.l1_acc?  The tests that make conv_hx_try pass a launch on (return 0) or that keep it off the masked whole-K epilogue; everything else it runs or refuses (-1).
+bool conv_hx_l1_ok(const ConvArgs& a) {
+    if (a.KS != 3 || !a.wq || (a.precision != PREC_BF16X3 && a.precision != PREC_BF16X1) || a.act == 1) return false;
+    if (!a.mask || !a.seed_ref || a.accumulate || a.res || a.pool_out || a.skip_out || a.avgpool) return false;
+    for (int s = 0; s < a.nsrc; s++) if ((a.src[s].ld & 3) || (a.src[s].sn & 3)) return false;
+    return (long)a.H * a.W * a.out_ld < (1L << 30);
+}
+
 // will conv_fwd_launch hand this launch to k_conv_hx (the only forward kernel that applies ConvSrc.bn_* while staging its input)?
 bool conv_src_lazy_ok(const ConvArgs& a) {
     if (a.KS != 3 || !a.wq || a.precision < PREC_F16X3 || a.precision > PREC_BF16X1 || a.act == 1) return false;
@@ -735,6 +764,7 @@ int conv_hx_try(const ConvArgs& a0, hipStream_t st, bool dry) {
     int bn = hx_pick_bn(a.Cout);
     a.Cout_pad = round_up(a.Cout, bn);      // (row padding of the packed weights: independent of the tile width chosen below)
     if (a.mask && a.accumulate) return -1;
+    if (a.l1_acc && !conv_hx_l1_ok(a)) return -1;      // (the caller asks first: no launch may drop the sum it was given)
     if (a.pool_out && (a.accumulate || a.mask)) return -1;
     if (a.avgpool) {      // average-pooled result (the caller asked conv_avgpool_ok): the latency kernel's pooled epilogue, or -- below -- a K-split launch whose slab reduce pools
         if ((a.H | a.W) & 1 || a.accumulate || a.mask || a.pool_out || a.skip_out || a.stats || a.lstm || a.precision != PREC_F16X3 || a.in_s16 || a.out_s16) return dry ? 0 : -1;

@@ -828,6 +828,7 @@ int conv_fwd_launch(const ConvArgs& a0, hipStream_t st) {
     if (a.pool_out || a.skip_out) return -1;      // fused max-pool / write-less epilogues exist in k_conv_hx only: the caller must not ask the other kernels for them
     const bool generic_only = a.act == 2 || a.mask != nullptr;      // ReLU / masked epilogues exist in k_conv_fwd only (VGG19 perceptual loss)
     if (a.seed_ref && !a.mask) return -1;
+    if (a.l1_acc) return -1;      // the feature-L1 sum of the seed epilogue exists in k_conv_hx only (the caller asks conv_hx_l1_ok first)
     const bool fold_epilogue = a.act == 3 || a.res != nullptr;      // LeakyReLU / residual epilogues (BatchNorm-folded roll-out): k_conv_fwd, k_conv_hx, k_conv_narrow
     if (!generic_only) {
         if (!fold_epilogue && conv_head_fwd_try(a, st) == 1) return 0;      // FinalBlock heads (-> 3 channels) on the 16-bit matrix pipe (conv_head.hip)

@@ -360,7 +360,8 @@ __global__ __launch_bounds__(256) void k_conv_c4(ConvArgs a, int tiles_x, int ti
     for (int i = tid; i < TAPS * NT * 64; i += 256) {
         int l = i & 63, tm = i >> 6;
         int m = tm % NT, t = tm / NT;
-        ws[i] = a.wp[((long)t * a.Cout_pad + og + m * 16 + (l & 15)) * a.Ktot + (l >> 4)];
+        const int row = og + m * 16 + (l & 15);              // (the last workgroup's NT x 16 rows may reach past Cout_pad, a multiple of the launcher's tile only: never read there)
+        ws[i] = row < a.Cout_pad ? a.wp[((long)t * a.Cout_pad + row) * a.Ktot + (l >> 4)] : 0.f;
     }
     float4 pre[NL];
     auto gload = [&](long tile) {

@@ -1804,6 +1804,7 @@ caddy_ctx* caddy_ctx_create(const caddy_config* cfg, float* params, float* grads
     if (const char* e = getenv("CADDY_MASK_FROM_X")) c->mask_from_x = atoi(e) != 0;      // A/B aid: 0 = BatchNorm backward reads the materialised output for the LeakyReLU slope (round-5 form)
     if (const char* e = getenv("CADDY_S16_GRADS")) c->s16_grads = atoi(e) != 0;      // A/B aid: 0 = every model gradient as fp32 (round-5 form)
     if (const char* e = getenv("CADDY_VGG_S16")) c->vgg_s16 = atoi(e) != 0;      // A/B aid: 0 = every VGG19 feature map as fp32 (round-4 form)
+    if (const char* e = getenv("CADDY_PERC_FUSE_L1")) c->perc_fuse_l1 = atoi(e) != 0;      // A/B aid: 0 = every VGG19 feature-L1 sum by the stand-alone kernel (round-6 form)
     if (const char* e = getenv("CADDY_PRECISION")) {      // A/B + parity aid: "exact" = every convolution on the exact-fp32 MFMA path
         if (!strcmp(e, "exact") || !strcmp(e, "0")) { c->prec_fwd = c->prec_bwd = PREC_FP32; c->vgg_precision = c->vgg_precision_bwd = PREC_FP32; }
         else if (!strcmp(e, "fwd")) { c->prec_bwd = PREC_FP32; c->vgg_precision_bwd = PREC_FP32; }
@@ -1826,6 +1827,7 @@ int caddy_debug_set_bn_paths(caddy_ctx* c, int small, int lazy, int epilogue_sta
 int caddy_debug_set_vgg_s16(caddy_ctx* c, int on) { c->vgg_s16 = on != 0; return 0; }
 int caddy_debug_set_s16_grads(caddy_ctx* c, int on) { c->s16_grads = on != 0; return 0; }
 int caddy_debug_set_perc_chunks(caddy_ctx* c, int n) { c->perc_chunks_force = n; return 0; }
+int caddy_debug_set_perc_fuse_l1(caddy_ctx* c, int on) { c->perc_fuse_l1 = on != 0; return 0; }
 long caddy_debug_s16_grad_count(caddy_ctx* c) { long n = 0; for (const GradFmt& g : c->gfmts) n += g.fmt ? 1 : 0; return n; }
 int caddy_debug_set_pack_merged(caddy_ctx* c, int on) { c->merged_pack = on != 0; c->pack_jobs.key = -1; for (auto& j : c->unpack_jobs) j.key = -1; return 0; }
 int caddy_debug_set_seeds_only(caddy_ctx* c, int on) { c->seeds_only = on != 0; return 0; }

@@ -189,6 +189,7 @@ struct caddy_ctx {
     VggState vgg;                    // VGG19 perceptual loss (perceptual.hip); enabled by caddy_config.perceptual
     int vgg_precision = PREC_F16X3, vgg_precision_bwd = PREC_BF16X3;   // ConvArgs.precision of the VGG convolutions (forward / dgrad); PREC_FP32 = exact
     bool vgg_s16 = true;             // VGG19 feature maps / feature gradients of well-filled layers as S16 tensors (caddy_debug_set_vgg_s16; CADDY_VGG_S16=0)
+    bool perc_fuse_l1 = true;        // feature-L1 sums of relu1_1 .. relu4_1 out of the seed epilogue of the dgrad above the tap instead of a pass of their own (ConvArgs.l1_acc; caddy_debug_set_perc_fuse_l1; CADDY_PERC_FUSE_L1=0)
     int prec_fwd = PREC_F16X3, prec_bwd = PREC_BF16X3;                 // ... of the model's wide 3x3 convolutions (caddy_set_precision; CADDY_PRECISION=exact)
     // ground-truth VGG19 branch overlapped with the forward pass on the side stream (perceptual.hip: vgg_gt_prefetch)
     T4 gt_img[3]{}; size_t gt_scratch_off = 0, gt_scratch_end = 0; bool gt_prefetched = false, perc_prefetch = true; hipEvent_t gt_done = nullptr;

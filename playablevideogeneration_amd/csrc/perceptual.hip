@@ -606,11 +606,9 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
             const double numel = (double)B * Trec * f.H * f.W * f.C;
             lv->numel[r][l] = numel;
             wl[l] = (float)(lambda * (l == 0 ? 1.0 : 2.0) / 3.0 / numel);
-            if (!dry) launch_feat_l1(st, f, taps[l], wl[l], l == 4 ? f.g : (float*)nullptr, gzs[li[4]], c->loss_acc + LOSS_PERC_R0 + 6 * r + 1 + l);
         }
-        if (lambda != 0.0) {
-            // backward of the reconstruction branch
-            for (int i = VGG_NCONV - 1; i >= 0; i--) {
+        // the dgrad launch of conv i (backward of the reconstruction branch)
+        auto dgrad_args = [&](int i) {
                 VggLayer& L = V.conv[i];
                 const T4& gz = R.a[i];
                 const T4& in = VS[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec);
@@ -628,6 +626,27 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
                     if (VS[i - 1].tap >= 0) { const T4& tp = taps[VS[i - 1].tap]; d.seed_ref = tp.d; d.seed_w = wl[VS[i - 1].tap]; d.seed_s16 = tp.fmt; }
                     d.out_s16 = gzs[i - 1] ? 1 : 0;
                 }
+                return d;
+        };
+        // Level sums.  relu1_1 .. relu4_1: the dgrad of the layer above the tap loads both maps for the sign of the L1 seed -- where that launch runs on a kernel that also sums
+        // |f_rec - f_gt| (conv_hx_l1_ok) it is handed the level's accumulator and the stand-alone pass over the two maps is skipped (caddy_ctx::perc_fuse_l1).  relu5_1 keeps
+        // k_feat_l1 (it writes the top seed), and so does every level when nothing is back-propagated.
+        bool l1_fused[5] = {false, false, false, false, false};
+        for (int l = 0; l < 5; l++) {
+            const T4& f = R.a[li[l]];
+            double* const lacc = c->loss_acc + LOSS_PERC_R0 + 6 * r + 1 + l;
+            if (l < 4 && lambda != 0.0 && c->perc_fuse_l1 && li[l] + 1 < VGG_NCONV && !VS[li[l] + 1].pool_before) {
+                const ConvArgs d = dgrad_args(li[l] + 1);
+                l1_fused[l] = d.seed_ref != nullptr && conv_hx_l1_ok(d);
+            }
+            if (!dry && !l1_fused[l]) launch_feat_l1(st, f, taps[l], wl[l], l == 4 ? f.g : (float*)nullptr, gzs[li[4]], lacc);
+        }
+        if (lambda != 0.0) {
+            // backward of the reconstruction branch
+            for (int i = VGG_NCONV - 1; i >= 0; i--) {
+                const T4& in = VS[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec);
+                ConvArgs d = dgrad_args(i);
+                if (i > 0 && VS[i - 1].tap >= 0 && l1_fused[VS[i - 1].tap]) d.l1_acc = c->loss_acc + LOSS_PERC_R0 + 6 * r + 1 + VS[i - 1].tap;
                 if (!dry) c->ck(conv_call(c, d, 2.0 * in.N * in.H * in.W * 9.0 * VS[i].cin * VS[i].cout, 4), "vgg dgrad");
                 if (VS[i].pool_before) {                                     // pooled input: route through the max-pool and the ReLU of a[i-1] (fp32 gradient of the pooled map -> gz_{i-1})
                     if (!dry) launch_maxpool_bwd(st, R.a[i - 1], (const float*)in.g, gzs[i - 1]);
