@@ -166,6 +166,36 @@ int caddy_load_lpips(caddy_ctx* ctx, const float* lpips_flat);
 int caddy_frame_lpips(caddy_ctx* ctx, const float* ref, const float* gen, int B, int T, float value_range, double* out_host);
 /* tests: bit l set = the level-l feature maps of both frames travelled as S16 tensors in some chunk of the last caddy_frame_lpips (evaluation/metrics/lpips.py:33); -1: no LPIPS context */
 int caddy_debug_lpips_tap_formats(caddy_ctx* ctx);
+/* --- FID of the dataset evaluation (evaluation/metrics/fid.py:140-159, called from evaluation/dataset_evaluator.py:225-250, dataset_evaluator_bair.py:130-150 and
+ *     dataset_evaluator_breakout.py:142-163): the 2048 pool_3 features of pytorch_fid/inception.py's InceptionV3([3]) per frame, on the implicit-GEMM convolution, pooling and
+ *     resize kernels of csrc/fid.hip.  A FID context is a metrics context of its own kind (every other caddy_frame_* / caddy_load_* entry point refuses it): frames of
+ *     height x width in chunks of max_frames; resize != 0 mirrors InceptionV3(resize_input=True) (inception.py:143-147: bilinear, 299 x 299), resize == 0 runs the trunk at the
+ *     frame's own size, at least 75 x 75 (else 0 / NULL and caddy_last_error).  The mean / covariance / Frechet distance are host-side fp64 (metrics.py).  Destroy with
+ *     caddy_ctx_destroy. --- */
+size_t caddy_fid_workspace_bytes(int max_frames, int height, int width, int resize);                                     /* pytorch_fid/inception.py:31-36 */
+caddy_ctx* caddy_fid_ctx_create(int max_frames, int height, int width, int resize, void* workspace, size_t bytes);       /* pytorch_fid/inception.py:31-36 */
+/* the network's tensors under the names of the pt_inception-2015-12-05 state dict (pytorch_fid/inception.py:13,200-201): per BasicConv2d {block}.{branch}.conv.weight (OIHW) and
+ * {block}.{branch}.bn.weight / .bias / .running_mean / .running_var, in graph order (94 convolutions; fc.* and AuxLogits.* are not part of the trunk);
+ * caddy_load_fid_inception takes a device buffer laid out by their offsets, folds every eval-mode BatchNorm2d(eps=0.001) into its convolution and packs the weights for both
+ * arithmetics.  The buffer is not referenced after the call. */
+int caddy_fid_param_count(void);
+int caddy_fid_param_info_get(int index, caddy_param_info* out);
+long caddy_fid_param_floats(void);
+int caddy_load_fid_inception(caddy_ctx* ctx, const float* flat);
+/* arithmetic of the Inception convolutions: 16 = split f16 (default; three products, the per-layer f16 range guard moves a layer that met |x| > 65504 to exact fp32) | 0 = exact
+ * fp32 MFMA.  The environment's CADDY_PRECISION=exact selects 0 at creation. */
+int caddy_set_fid_precision(caddy_ctx* ctx, int forward);
+/* evaluation/metrics/fid.py:98-137 (get_activations): frames = n x (3, height, width) planar fp32 in [0, 1] on the device; out_host (host memory) receives n x 2048 doubles.
+ * Bit-reproducible, and independent of max_frames: every frame's features depend on that frame alone.  Waits for the stream. */
+int caddy_fid_features(caddy_ctx* ctx, const float* frames, int n, double* out_host);
+/* tests: the output of block 0..3 of InceptionV3.BLOCK_INDEX_BY_DIM (pytorch_fid/inception.py:24-29: 64, 192, 768 and 2048 channels) for the frames of the LAST chunk of the last
+ * caddy_fid_features, NCHW fp32 into a device buffer; caddy_debug_fid_fallback_layers: convolutions the range guard moved to exact fp32 (-1: no FID context) */
+int caddy_debug_fid_block(caddy_ctx* ctx, int block, float* dst_nchw);
+int caddy_debug_fid_fallback_layers(caddy_ctx* ctx);
+/* measurement: on != 0 records events at the stage boundaries of the following chunks; ms5 (nullable) receives the times of the last chunk's input stage, stem, 35 x 35, 17 x 17
+ * and 8 x 8 stages (pytorch_fid/inception.py:83-123).  caddy_fid_macs_per_frame: multiply-accumulates of the 94 convolutions for one frame, counted from the graph. */
+int caddy_debug_fid_stage_ms(caddy_ctx* ctx, int on, float* ms5);
+double caddy_fid_macs_per_frame(int height, int width, int resize);
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per
@@ -331,6 +361,16 @@ long caddy_bn_calls(caddy_ctx* ctx, int i, char* name_out128);
 struct ConvArgs; struct WgradArgs; struct PackDesc; struct TV;
 int caddy_k_conv_fwd(const struct ConvArgs* a, void* stream);
 int caddy_k_conv_wgrad(const struct WgradArgs* a, void* stream);
+/* kernels of the FID feature network (csrc/fid.h; reference: the Conv2d / BatchNorm2d / pooling / F.interpolate calls of torchvision's Inception3 as patched by
+ * pytorch_fid/inception.py:143-150,205-322) */
+struct IgemmArgs;
+size_t caddy_k_igemm_weight_bytes(int Cin, int Cout, int KH, int KW);
+int caddy_k_igemm_pack(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps, const float* bias_in, int Cin, int Cout, int KH, int KW,
+                       void* w32, void* w16, float* bias_out, void* stream);
+int caddy_k_conv_igemm(const struct IgemmArgs* a, void* stream);
+int caddy_k_fid_pool(const struct TV* in, const struct TV* out, int mode, void* stream);      /* 0: MaxPool2d(3, 2); 1: avg_pool2d(3, 1, 1, count_include_pad=False); 2: max_pool2d(3, 1, 1) */
+int caddy_k_fid_global_avg(const struct TV* in, double* out, void* stream);
+int caddy_k_fid_stage(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, void* stream);
 int caddy_k_conv_took_direct(void);      /* 1: this thread's last caddy_k_conv_fwd ran on the latency kernel (ConvArgs.direct_ok; model/main_model/model.py:570-607 batch-1 roll-out layers) */
 /* BatchNorm fused with the convolutions around it (reference: the conv -> BatchNorm2d -> LeakyReLU chains of model/layers/residual_block.py:51-68,
  * same_block.py:34-47, up_block.py:31-45): per-tile partial sums from the producing conv's epilogue (ConvArgs.stats) -> finalisation without a pass over

@@ -5,6 +5,7 @@
 #include "net.h"
 #include "frame_metrics.h"
 #include "detection.h"
+#include "fid.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1738,7 +1739,7 @@ int caddy_frame_metrics(caddy_ctx* c, const float* ref, const float* gen, int B,
 }
 
 int caddy_platform_positions(caddy_ctx* c, const float* obs, int B, int T, int row, float lo, float hi, int min_run, int* out_host) {
-    if (!c || !c->metrics_only) { set_error("caddy_platform_positions needs a context from caddy_metrics_ctx_create"); return -2; }
+    if (!c || !c->metrics_only || c->fid) { set_error("caddy_platform_positions needs a context from caddy_metrics_ctx_create"); return -2; }
     c->fail = false;
     if (!obs || !out_host) { set_error("null input"); return -2; }
     const int H = c->cfg.height, W = c->cfg.width;
@@ -1819,6 +1820,7 @@ void caddy_ctx_destroy(caddy_ctx* c) {
     if (c && c->gstream) { if (c->graph_exec) hipStreamSynchronize(c->stream); hipStreamSynchronize(c->gstream); c->drop_graph(); hipStreamDestroy(c->gstream); }
     if (c) for (ConvL* L : c->convs) if (L->off_ev) hipEventDestroy(L->off_ev);
     if (c && c->dstream) { hipStreamSynchronize(c->dstream); hipStreamDestroy(c->dstream); if (c->d_done) hipEventDestroy(c->d_done); }
+    fid_free(c);
     delete c;
 }
 int caddy_set_stream(caddy_ctx* c, void* s) { c->stream = (hipStream_t)s; return 0; }

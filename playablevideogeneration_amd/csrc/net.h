@@ -241,6 +241,7 @@ struct caddy_ctx {
     bool metrics_only = false;
     double* fm_slab = nullptr;       // per (frame, tile) partials of the fused pass (cfg.batch = max_frames frames)
     double* fm_out = nullptr;        // CADDY_FM_COUNT x max_frames results of the current chunk
+    struct FidState* fid = nullptr;  // FID feature network (caddy_fid_ctx_create; fid.hip owns it)
 
     // ---- optional per-launch timing of the conv kernels (HIP events on the launch stream; bench.py roofline) ----
     struct ProfRec { hipEvent_t a, b; int fam; double flops; int P, K, Cout, KS, kind; double bytes; };   // kind: 0 fwd, 1 dgrad (accumulate), 2 wgrad

@@ -5,7 +5,9 @@ Per frame, on the device: mse, motion_masked_mse, psnr, ssim and -- when VGG19 w
 `evaluation.vgg19_from_torchvision`, the loader of Trainer._find_vgg_weights) -- vgg_sim, all from one fused HIP pass (metrics.FrameMetrics).  The
 keys are those of compute_positional_statistics: {m}/avg, {m}/var, {m}/{i}, {m}/{i}/var.  With LPIPS weights (`evaluation.lpips_weights`, or
 `evaluation.lpips_vgg16_weights` + `evaluation.lpips_linear_weights`: metrics.find_lpips_weights) `lpips` is added (evaluation/metrics/lpips.py:14,33, on the
-HIP path: metrics.LPIPS); without them the keys are unchanged.  FID, FVD, IS and the plots need further pretrained networks and are not computed.  The per-dataset evaluators that add the detection and action metrics of Breakout and BAIR are
+HIP path: metrics.LPIPS); without them the keys are unchanged.  With Inception weights (`evaluation.fid_inception_weights`: metrics.find_fid_weights; `evaluation.fid_resize_input`,
+default true, is InceptionV3's resize_input) `fid` is added (evaluation/metrics/fid.py:140-159): the features of every frame of both datasets are collected inside the one batch
+loop (the reference makes two further passes over each loader), the statistics and the Frechet distance are host fp64.  FVD, IS and the plots are not computed.  The per-dataset evaluators that add the detection and action metrics of Breakout and BAIR are
 dataset_evaluator_breakout and dataset_evaluator_bair (ActionSpaceEvaluator below).
 """
 from typing import Dict
@@ -42,9 +44,16 @@ class DatasetEvaluator:
         self.lpips_state = M.find_lpips_weights(config["evaluation"])
         if self.lpips_state is None:
             self.logger.print("- lpips skipped: no LPIPS weights configured (evaluation.lpips_weights, or evaluation.lpips_vgg16_weights + evaluation.lpips_linear_weights)")
+        self.fid_state = M.find_fid_weights(config["evaluation"])
+        self.fid_resize = bool(config["evaluation"].get("fid_resize_input", True))
+        self._fid_features = ([], [])
+        if self.fid_state is None:
+            self.logger.print("- fid skipped: no Inception weights configured (evaluation.fid_inception_weights)")
         self.logger.print(self.NOT_COMPUTED)
         if self.lpips_state is not None:
             self.logger.print("- lpips is computed (LPIPS weights configured): the line above applies to it no longer")
+        if self.fid_state is not None:
+            self.logger.print("- fid is computed (Inception weights configured): the line above applies to it no longer")
 
     @staticmethod
     def check_range(values: Dict[str, torch.Tensor], which: str):
@@ -74,6 +83,21 @@ class DatasetEvaluator:
             values["lpips"] = M.lpips(reference_observations, generated_observations, self.lpips_state, 1.0)
         return values
 
+    def collect_fid_features(self, reference_observations: torch.Tensor, generated_observations: torch.Tensor) -> None:
+        """Inception features of this batch's frames, every frame of every sequence a sample (evaluation/metrics/fid.py:119-135); nothing without weights"""
+        if self.fid_state is None:
+            return
+        self._fid_features[0].append(M.inception_features(reference_observations, self.fid_state, resize=self.fid_resize).numpy())
+        self._fid_features[1].append(M.inception_features(generated_observations, self.fid_state, resize=self.fid_resize).numpy())
+
+    def fid_results(self) -> Dict:
+        """{"fid": float} over the features collected since the last call (evaluation/metrics/fid.py:140-159); {} without weights"""
+        if self.fid_state is None:
+            return {}
+        ref, gen = (np.concatenate(f, axis=0) for f in self._fid_features)
+        self._fid_features = ([], [])
+        return {"fid": float(M.fid_from_features(ref, gen))}
+
     def metric_names(self, names):
         return [m for m in names if m != "vgg_sim" or self.vgg_state is not None] + (["lpips"] if self.lpips_state is not None else [])
 
@@ -91,9 +115,11 @@ class DatasetEvaluator:
                 self.check_range(values, "gen")
                 for m in names:
                     acc[m].append(values[m].numpy())
+                self.collect_fid_features(reference_observations, generated_observations)
         results = {}
         for m in names:
             results.update(self.compute_positional_statistics(np.concatenate(acc[m], axis=0), m))
+        results.update(self.fid_results())
         return results
 
 
@@ -150,6 +176,7 @@ class ActionSpaceEvaluator(DatasetEvaluator):
                 self.check_range(values, "gen")
                 for m in names:
                     acc[m].append(values[m].numpy())
+                self.collect_fid_features(reference_observations, generated_observations)
                 found = self.detect(reference_observations, generated_observations)
                 for k, v in found.items():
                     detections.setdefault(k, []).append(v)
@@ -167,6 +194,7 @@ class ActionSpaceEvaluator(DatasetEvaluator):
         if not accuracy:
             self.logger.print("- Warning: action accuracy results could not be computed")
         results.update(accuracy)
+        results.update(self.fid_results())
         return results
 
 

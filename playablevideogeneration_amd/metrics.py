@@ -1,4 +1,4 @@
-"""Frame-quality metrics of the paper's evaluation protocol that need no third-party network.
+"""Frame-quality metrics of the paper's evaluation protocol; pretrained networks (VGG19, LPIPS, Inception) take their weights from the caller.
 Inputs are (bs, observations_count, channels, height, width) tensors in the same value range; results are (bs, observations_count).
 
     mse / psnr                  evaluation/metrics/mse.py:13-24, psnr.py:11-31 -- plain torch expressions
@@ -11,8 +11,12 @@ Inputs are (bs, observations_count, channels, height, width) tensors in the same
 
 The HIP-backed metrics run on a metrics context of libcaddy_hip.so (caddy_metrics_ctx_create), cached per frame geometry; there is no torch fallback.
 `set_library` points them at another build of the same kernels (the tests' host simulator).
-LPIPS needs its weights from the caller (a torchvision vgg16 state dict plus the package's five `lin` tensors, see lpips_state): nothing is downloaded.
-(FID / FVD / IS and the Tennis detector depend on further pretrained networks and stay out of scope.)"""
+    fid                         evaluation/metrics/fid.py:140-159 (pytorch_fid InceptionV3([3]) features)  -- the Inception-v3 trunk on the implicit-GEMM convolution,
+                                                                                                          pooling and resize kernels of csrc/fid.hip; mean, covariance and
+                                                                                                          the Frechet distance in fp64 on the host
+LPIPS needs its weights from the caller (a torchvision vgg16 state dict plus the package's five `lin` tensors, see lpips_state), FID the pt_inception-2015-12-05 state dict
+(fid_inception_state): nothing is downloaded.
+(FVD -- I3D, 3-D convolutions --, the Inception Score and the Tennis detector stay out of scope.)"""
 import ctypes as C
 import re
 from typing import Dict, Optional
@@ -44,6 +48,7 @@ def set_library(lib) -> None:
     _default_lib = lib
     _contexts.clear()
     _lpips_contexts.clear()
+    _fid_contexts.clear()
 
 
 def _bind(lib):
@@ -65,6 +70,20 @@ def _bind(lib):
         lib.caddy_load_lpips.argtypes = [C.c_void_p, C.c_void_p]
         lib.caddy_frame_lpips.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         lib.caddy_debug_lpips_tap_formats.argtypes = [C.c_void_p]
+        lib.caddy_fid_workspace_bytes.restype = C.c_size_t
+        lib.caddy_fid_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.caddy_fid_ctx_create.restype = C.c_void_p
+        lib.caddy_fid_ctx_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        lib.caddy_fid_param_floats.restype = C.c_long
+        lib.caddy_fid_param_info_get.argtypes = [C.c_int, C.c_void_p]
+        lib.caddy_load_fid_inception.argtypes = [C.c_void_p, C.c_void_p]
+        lib.caddy_set_fid_precision.argtypes = [C.c_void_p, C.c_int]
+        lib.caddy_fid_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        lib.caddy_debug_fid_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.caddy_debug_fid_fallback_layers.argtypes = [C.c_void_p]
+        lib.caddy_debug_fid_stage_ms.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.caddy_fid_macs_per_frame.restype = C.c_double
+        lib.caddy_fid_macs_per_frame.argtypes = [C.c_int, C.c_int, C.c_int]
         lib._caddy_metrics_bound = True
     return lib
 
@@ -374,6 +393,204 @@ def lpips(reference_observations: torch.Tensor, generated_observations: torch.Te
     if lpips_weights is None:
         raise ValueError("lpips needs LPIPS weights (see lpips_state)")
     return _cached_lpips(reference_observations, lpips_weights, lib)(reference_observations, generated_observations, value_range, return_levels)
+
+
+# ---- FID (caddy_fid_features + host fp64 statistics) ----
+FID_FRAMES_256 = 64       # frames per Inception chunk at 256 x 256 with the 299 x 299 resize: ~0.9 GB of activations
+FID_DIM = 2048
+FID_BLOCK_CHANNELS = (64, 192, 768, 2048)      # InceptionV3.BLOCK_INDEX_BY_DIM (pytorch_fid/inception.py:24-29)
+_fid_contexts: Dict = {}
+_fid_names = None
+
+
+def fid_param_table(lib=None):
+    """[(name, offset, shape)] of caddy_fid_param_info_get: the trunk's tensors under the pt_inception-2015-12-05 names, in graph order"""
+    global _fid_names
+    from . import _lib
+    from .engine import ParamInfo
+    if _fid_names is None or lib is not None:
+        L = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
+        info, table = ParamInfo(), []
+        for i in range(L.caddy_fid_param_count()):
+            L.caddy_fid_param_info_get(i, C.byref(info))
+            table.append((info.name.decode(), int(info.offset), tuple(info.shape[:info.ndim])))
+        if lib is not None:
+            return table
+        _fid_names = table
+    return _fid_names
+
+
+def fid_inception_state(state_dict: Dict[str, torch.Tensor], lib=None) -> Dict[str, torch.Tensor]:
+    """The trunk's tensors of the pt_inception-2015-12-05 state dict (pytorch_fid/inception.py:13,200-201) under the names of caddy_fid_param_info_get.  Accepts the
+    keys as they are, under a `module.` / `model.` prefix, or wrapped in {"state_dict": ...}; `fc.*`, `AuxLogits.*` and `num_batches_tracked` are ignored.
+    A missing tensor raises CaddyError naming it."""
+    from .engine import CaddyError
+    src = state_dict.get("state_dict", state_dict) if isinstance(state_dict, dict) else state_dict
+    out = {}
+    for name, _, _ in fid_param_table(lib):
+        key = next((k for k in (name, "module." + name, "model." + name) if k in src), None)
+        if key is None:
+            raise CaddyError(f"FID Inception weights lack {name}")
+        out[name] = src[key]
+    return out
+
+
+def find_fid_weights(cfg) -> Optional[Dict[str, torch.Tensor]]:
+    """config["evaluation"] -> fid_inception_state(...) of `fid_inception_weights` (a path or a dict); None when it is not configured.  Nothing is downloaded."""
+    src = cfg.get("fid_inception_weights", None)
+    if src is None:
+        return None
+    if isinstance(src, str):
+        src = torch.load(src, map_location="cpu", weights_only=True)
+    return fid_inception_state(src)
+
+
+class InceptionFeatures:
+    """The FID feature network for frames of height x width: pytorch_fid's InceptionV3([3], resize_input=resize) on csrc/fid.hip.  Calling it on (bs, T, 3, H, W) or
+    (n, 3, H, W) frames in [0, 1] returns an (n, 2048) float64 CPU tensor; more than `max_frames` frames run in chunks."""
+
+    def __init__(self, height: int, width: int, max_frames: int, weights, resize: bool = True, lib=None, device=None):
+        from . import _lib
+        from .engine import CaddyError
+        self.lib = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
+        kind = getattr(self.lib, "_caddy_device_type", "cuda")
+        self.device = torch.device(device) if device is not None else torch.device(kind)
+        self.H, self.W, self.max_frames, self.resize = int(height), int(width), int(max_frames), bool(resize)
+        self._err = lambda: self.lib.caddy_last_error().decode()
+        table = fid_param_table(self.lib)
+        state = fid_inception_state(weights, self.lib)
+        n = self.lib.caddy_fid_workspace_bytes(self.max_frames, self.H, self.W, int(self.resize))
+        if n == 0:
+            raise CaddyError(self._err())
+        raw = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+        self._ws = raw
+        self.ws_bytes = n
+        self.ctx = self.lib.caddy_fid_ctx_create(self.max_frames, self.H, self.W, int(self.resize), raw.data_ptr() + (-raw.data_ptr()) % 256, n)
+        if not self.ctx:
+            raise CaddyError(self._err())
+        flat = torch.zeros(self.lib.caddy_fid_param_floats(), dtype=torch.float32)
+        for name, off, shape in table:
+            t = state[name].detach().to(torch.float32)
+            if tuple(t.shape) != shape:
+                raise CaddyError(f"FID Inception {name}: shape {tuple(t.shape)}, expected {shape}")
+            flat[off:off + t.numel()] = t.reshape(-1)
+        flat = flat.to(self.device)
+        self._stream()
+        self._check(self.lib.caddy_load_fid_inception(self.ctx, flat.data_ptr()))
+
+    _check = FrameMetrics._check
+    _stream = FrameMetrics._stream
+    __del__ = FrameMetrics.__del__
+
+    def set_precision(self, forward: int):
+        """arithmetic of the convolutions: 16 (split f16, default) | 0 (exact fp32)"""
+        self._check(self.lib.caddy_set_fid_precision(self.ctx, int(forward)))
+
+    def fallback_layers(self) -> int:
+        return int(self.lib.caddy_debug_fid_fallback_layers(self.ctx))
+
+    def __call__(self, observations: torch.Tensor) -> torch.Tensor:
+        o = observations
+        if o.dim() == 5:
+            o = o.reshape((-1,) + tuple(o.shape[2:]))      # TensorFolder.flatten (evaluation/metrics/fid.py:123): every frame of every sequence is a sample
+        if o.dim() != 4 or o.shape[1] != 3 or tuple(o.shape[2:]) != (self.H, self.W):
+            raise ValueError(f"expected (bs, observations_count, 3, {self.H}, {self.W}) or (n, 3, {self.H}, {self.W}) frames, got {tuple(observations.shape)}")
+        n = int(o.shape[0])
+        o = o.detach().to(self.device, torch.float32).contiguous()
+        out = torch.empty(n, FID_DIM, dtype=torch.float64)
+        self._stream()
+        self._check(self.lib.caddy_fid_features(self.ctx, o.data_ptr(), n, out.data_ptr()))
+        self.last_frames = (n - 1) % self.max_frames + 1
+        return out
+
+    def block(self, index: int) -> torch.Tensor:
+        """output of block `index` (0..3) for the frames of the last chunk of the last call, (frames, C, h, w) float32 on the CPU (caddy_debug_fid_block)"""
+        hs = _fid_block_sizes(self.H, self.W, self.resize)
+        h, w = hs[index]
+        buf = torch.empty(self.last_frames, FID_BLOCK_CHANNELS[index], h, w, dtype=torch.float32, device=self.device)
+        self._check(self.lib.caddy_debug_fid_block(self.ctx, int(index), buf.data_ptr()))
+        return buf.cpu()
+
+    def stage_times(self, on: bool = True, read: bool = False):
+        """per-stage milliseconds of the last timed chunk (input stage, stem, 35 x 35, 17 x 17, 8 x 8) when `read`; `on` switches the event recording"""
+        ms = (C.c_float * 5)()
+        self._check(self.lib.caddy_debug_fid_stage_ms(self.ctx, int(on), ms if read else None))
+        return list(ms) if read else None
+
+
+def _fid_block_sizes(H: int, W: int, resize: bool):
+    """spatial sizes of the four block outputs (the trunk's unpadded 3 x 3 convolutions and stride-2 poolings)"""
+    def chain(s):
+        s = 299 if resize else s
+        a = (s - 3) // 2 + 1 - 2
+        p1 = (a - 3) // 2 + 1
+        p2 = (p1 - 2 - 3) // 2 + 1
+        return p1, p2, (p2 - 3) // 2 + 1
+    (h0, h1, h2), (w0, w1, w2) = chain(int(H)), chain(int(W))
+    return [(h0, w0), (h1, w1), (h2, w2), (1, 1)]
+
+
+def _cached_fid(observations: torch.Tensor, weights, lib, resize: bool = True) -> InceptionFeatures:
+    """the FID context of this library, device, frame geometry and weights (cached like _cached_lpips)"""
+    H, W = int(observations.shape[-2]), int(observations.shape[-1])
+    n = int(np.prod(observations.shape[:-3]))
+    lib = lib if lib is not None else _default_lib
+    key = (id(lib), str(observations.device), H, W, bool(resize), id(weights))
+    ctx = _fid_contexts.get(key)
+    if ctx is None:
+        area = 299 * 299 if resize else H * W
+        want = min(n, max(1, FID_FRAMES_256 * 299 * 299 // area))
+        ctx = InceptionFeatures(H, W, min(want, 1024), weights, resize, lib)
+        ctx._keep = weights      # (the cache key holds its id)
+        _fid_contexts[key] = ctx
+    return ctx
+
+
+def inception_features(observations: torch.Tensor, weights, lib=None, resize: bool = True) -> torch.Tensor:
+    """(bs, T, 3, H, W) or (n, 3, H, W) frames in [0, 1] -> (n, 2048) float64 pool_3 features (evaluation/metrics/fid.py:98-137)"""
+    if weights is None:
+        raise ValueError("FID needs Inception weights (see fid_inception_state)")
+    return _cached_fid(observations, weights, lib, resize)(observations)
+
+
+def activation_statistics(features):
+    """(mu, sigma) of evaluation/metrics/fid.py:93-96: the mean and np.cov(features, rowvar=False), fp64 on the host"""
+    act = np.asarray(features, dtype=np.float64)
+    return np.mean(act, axis=0), np.cov(act, rowvar=False)
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2) -> float:
+    """|mu1 - mu2|^2 + Tr(S1 + S2 - 2 sqrt(S1 S2)) (evaluation/metrics/fid.py:24-75).  Tr sqrt(S1 S2) is the sum of the square roots of the eigenvalues of the symmetric
+    positive semi-definite S1^(1/2) S2 S1^(1/2) (similar to S1 S2), from two symmetric eigen-decompositions in fp64 with eigenvalues below the rank tolerance set to 0: the quantity the
+    reference's scipy.linalg.sqrtm computes, without its complex or singular branches."""
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, np.float64)), np.atleast_1d(np.asarray(mu2, np.float64))
+    s1, s2 = np.atleast_2d(np.asarray(sigma1, np.float64)), np.atleast_2d(np.asarray(sigma2, np.float64))
+    if mu1.shape != mu2.shape or s1.shape != s2.shape:
+        raise ValueError("Training and test statistics have different dimensions")
+    def significant(values):
+        # eigh returns the zero eigenvalues of a rank-deficient matrix (N samples < d dimensions: rank <= N - 1) as noise of size eps |A|, and the square root turns 1e-17 into
+        # 3e-9 -- times ~2000 null directions that is 1e-5 of spurious trace.  Eigenvalues below d eps max|lambda| (the tolerance of numpy.linalg.matrix_rank) are zeros.
+        top = float(values.max()) if values.size else 0.0
+        return np.where(values > values.size * np.finfo(np.float64).eps * max(top, 0.0), values, 0.0)
+    w, v = np.linalg.eigh((s1 + s1.T) / 2)
+    root = (v * np.sqrt(significant(w))) @ v.T
+    m = root @ ((s2 + s2.T) / 2) @ root
+    ev = np.linalg.eigvalsh((m + m.T) / 2)
+    tr_covmean = float(np.sqrt(significant(ev)).sum())
+    diff = mu1 - mu2
+    return float(diff.dot(diff) + np.trace(s1) + np.trace(s2) - 2.0 * tr_covmean)
+
+
+def fid_from_features(reference_features, generated_features) -> float:
+    m1, s1 = activation_statistics(reference_features)
+    m2, s2 = activation_statistics(generated_features)
+    return frechet_distance(m1, s1, m2, s2)
+
+
+def fid(reference_observations: torch.Tensor, generated_observations: torch.Tensor, weights, lib=None, resize: bool = True) -> float:
+    """FID between two sets of frames in [0, 1] (evaluation/metrics/fid.py:140-159); every frame of every sequence is a sample"""
+    return fid_from_features(inception_features(reference_observations, weights, lib, resize).numpy(),
+                             inception_features(generated_observations, weights, lib, resize).numpy())
 
 
 def rollout_quality(model, batch_tuple, ground_truth_observations_init: int = 1, gumbel_temperature: float = 1.0) -> dict:
