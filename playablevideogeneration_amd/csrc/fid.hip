@@ -13,7 +13,7 @@
 //
 // Determinism: no atomics except the integer OR of the range flag; every output element has one writer and a fixed summation order, so two runs -- and two chunkings of the same
 // frames -- give identical bits.
-#include "net.h"
+#include "eval_ctx.h"
 #include "fid.h"
 #include <cstdio>
 #include <cstring>
@@ -488,50 +488,33 @@ bool fid_args_ok(int max_frames, int H, int W, int resize) {
     if (!resize && (H < 75 || W < 75)) { set_error("caddy_fid: without the 299 x 299 resize the Inception trunk needs frames of at least 75 x 75"); return false; }
     return true;
 }
-caddy_ctx* make_fid_ctx(int max_frames, int H, int W, int resize, void* ws, size_t act_cap) {
-    caddy_ctx* c = new caddy_ctx();
-    c->metrics_only = true; c->dry = ws == nullptr;
-    c->cfg.batch = max_frames; c->cfg.seq_len = 1; c->cfg.height = H; c->cfg.width = W;
-    c->vgg.kind = VGG_KIND_FID;
-    c->persist.base = (char*)ws; c->persist.cap = (size_t)-1;
-    FidState* F = new FidState();
-    c->fid = F;
-    F->resize = resize ? 1 : 0; F->Hn = resize ? 299 : H; F->Wn = resize ? 299 : W;
-    long off = 0;
-    for (const FidSpec& s : fid_specs()) {
-        FidLayer L; L.s = s; L.off = off; off += fid_layer_floats(s);
-        const size_t wb = igemm_weight_bytes(s.cin, s.cout, s.kh, s.kw);
-        L.w32 = c->persist.alloc(wb); L.w16 = c->persist.alloc(wb);
-        L.bias = (float*)c->persist.alloc((size_t)s.cout * 4);
-        F->L.push_back(L);
-    }
-    c->sat_flag = (unsigned*)c->persist.alloc(sizeof(unsigned) * 2 * CADDY_N_FLAGS);
-    F->feat = (double*)c->persist.alloc(sizeof(double) * FID_DIM * (size_t)max_frames);
-    const size_t pbytes = (c->persist.high + 4095) & ~(size_t)4095;
-    c->act.base = (char*)ws + pbytes; c->act.cap = act_cap; c->grad_delta = 0;
-    c->act.reset();
-    return c;
-}
 void fid_chunk(caddy_ctx* c, const float* frames, int nf) {
     FidWalk w; w.c = c; w.F = c->fid;
     w.run(frames, nf, c->cfg.height, c->cfg.width, c->fid->Hn, c->fid->Wn);
 }
-void fid_sizes(int max_frames, int H, int W, int resize, size_t* persist, size_t* act) {
-    caddy_ctx* c = make_fid_ctx(max_frames, H, W, resize, nullptr, (size_t)1 << 50);
-    fid_chunk(c, nullptr, max_frames);
-    *persist = (c->persist.high + 4095) & ~(size_t)4095;
-    *act = ((c->act.high + 4095) & ~(size_t)4095) + 4096;
-    fid_free(c);
-    delete c;
-}
-int fid_finish(caddy_ctx* c) {
-    if (c->act.overflow() && !c->fail) { c->fail = true; set_error("activation arena overflow (workspace smaller than caddy_fid_workspace_bytes)"); }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess && !c->fail) { c->fail = true; set_error(std::string("HIP error: ") + hipGetErrorString(e)); }
-    return c->fail ? -1 : 0;
+const char* const FID_SIZER = "caddy_fid_workspace_bytes";
+// FID kind (caddy_fid_ctx_create): both packed forms and the folded bias of every Inception layer, 2048 feature doubles per frame; the activation arena of one chunk of the walk
+EvalKind fid_kind(int max_frames, int H, int W, int resize) {
+    return {CTX_FID, max_frames, H, W,
+            [=](caddy_ctx* c) {
+                FidState* F = new FidState();
+                c->fid = F;
+                F->resize = resize ? 1 : 0; F->Hn = resize ? 299 : H; F->Wn = resize ? 299 : W;
+                long off = 0;
+                for (const FidSpec& s : fid_specs()) {
+                    FidLayer L; L.s = s; L.off = off; off += fid_layer_floats(s);
+                    const size_t wb = igemm_weight_bytes(s.cin, s.cout, s.kh, s.kw);
+                    L.w32 = c->persist.alloc(wb); L.w16 = c->persist.alloc(wb);
+                    L.bias = (float*)c->persist.alloc((size_t)s.cout * 4);
+                    F->L.push_back(L);
+                }
+                F->feat = (double*)c->persist.alloc(sizeof(double) * FID_DIM * (size_t)max_frames);
+            },
+            [=](caddy_ctx* c) { fid_chunk(c, nullptr, max_frames); },
+            FID_SIZER};
 }
 bool fid_ctx_ok(caddy_ctx* c, const char* who) {
-    if (!c || !c->fid) { set_error(std::string(who) + " needs a context from caddy_fid_ctx_create"); return false; }
+    if (!ctx_needs(c, CTX_FID, who)) return false;
     c->fail = false;
     return true;
 }
@@ -546,19 +529,11 @@ void fid_free(caddy_ctx* c) {
 
 extern "C" {
 size_t caddy_fid_workspace_bytes(int max_frames, int height, int width, int resize) {
-    if (!fid_args_ok(max_frames, height, width, resize)) return 0;
-    size_t p, a; fid_sizes(max_frames, height, width, resize, &p, &a);
-    return p + a + 4096;
+    return fid_args_ok(max_frames, height, width, resize) ? eval_workspace_bytes(fid_kind(max_frames, height, width, resize)) : 0;
 }
 caddy_ctx* caddy_fid_ctx_create(int max_frames, int height, int width, int resize, void* workspace, size_t bytes) {
-    if (!fid_args_ok(max_frames, height, width, resize)) return nullptr;
-    if (!workspace) { set_error("null buffer"); return nullptr; }
-    if ((uintptr_t)workspace & 255) { set_error("the workspace must be 256-byte aligned"); return nullptr; }
-    size_t p, a; fid_sizes(max_frames, height, width, resize, &p, &a);
-    if (bytes < p + a) { set_error("workspace too small (see caddy_fid_workspace_bytes)"); return nullptr; }
-    caddy_ctx* c = make_fid_ctx(max_frames, height, width, resize, workspace, a);
-    hipMemset(c->sat_flag, 0, sizeof(unsigned) * 2 * CADDY_N_FLAGS);
-    if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) c->fid->precision = PREC_FP32;
+    caddy_ctx* c = fid_args_ok(max_frames, height, width, resize) ? eval_ctx_create(fid_kind(max_frames, height, width, resize), workspace, bytes) : nullptr;
+    if (c) if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) c->fid->precision = PREC_FP32;
     return c;
 }
 int caddy_fid_param_count(void) { return 5 * (int)fid_specs().size(); }
@@ -589,7 +564,7 @@ int caddy_load_fid_inception(caddy_ctx* c, const float* flat) {
     }
     hipStreamSynchronize(c->stream);      // the caller's buffer is not referenced after this call
     c->fid->loaded = !c->fail;
-    return fid_finish(c);
+    return finish(c, FID_SIZER);
 }
 int caddy_set_fid_precision(caddy_ctx* c, int forward) {
     if (!fid_ctx_ok(c, "caddy_set_fid_precision")) return -2;
@@ -603,28 +578,19 @@ int caddy_fid_features(caddy_ctx* c, const float* frames, int n, double* out_hos
     if (n < 1) { set_error("caddy_fid_features: n must be positive"); return -2; }
     FidState* F = c->fid;
     if (!F->loaded) { set_error("caddy_fid_features: no Inception weights were loaded (caddy_load_fid_inception)"); return -2; }
-    const int M = c->cfg.batch, NL = (int)F->L.size();
     const long fr = 3L * c->cfg.height * c->cfg.width;
-    hipStream_t st = c->stream;
-    std::vector<unsigned> v(NL);
-    for (long n0 = 0; n0 < n; n0 += M) {      // chunks of max_frames frames (the activation arena)
-        const int nf = (int)std::min<long>(M, n - n0);
+    for_chunks(c, n, [&](long n0, int nf) {      // (the activation arena holds max_frames frames)
+        // a layer of the split-f16 path that left the f16 range moves to exact fp32 and the chunk runs again
         for (int attempt = 0; attempt < 2; attempt++) {
             fid_chunk(c, frames + n0 * fr, nf);
-            if (c->fail) return fid_finish(c);
-            if (F->precision == PREC_FP32) break;
-            // f16 range guard of the split-f16 path: a layer that met |x| > 65504 moves to exact fp32 for good and the chunk runs again
-            hipMemcpyAsync(v.data(), c->sat_flag, sizeof(unsigned) * NL, hipMemcpyDeviceToHost, st);
-            hipStreamSynchronize(st);
-            bool again = false;
-            for (int i = 0; i < NL; i++) if (v[i] && !c->layer_fallback[i]) { c->layer_fallback[i] = true; c->n_fallback++; again = true; }
-            if (!again) break;
-            hipMemsetAsync(c->sat_flag, 0, sizeof(unsigned) * 2 * CADDY_N_FLAGS, st);
+            if (c->fail) return false;
+            if (F->precision == PREC_FP32 || !range_guard_retry(c, 0, (int)F->L.size())) break;
         }
-        hipMemcpyAsync(out_host + n0 * FID_DIM, F->feat, sizeof(double) * FID_DIM * nf, hipMemcpyDeviceToHost, st);
-        hipStreamSynchronize(st);
-    }
-    return fid_finish(c);
+        hipMemcpyAsync(out_host + n0 * FID_DIM, F->feat, sizeof(double) * FID_DIM * nf, hipMemcpyDeviceToHost, c->stream);
+        hipStreamSynchronize(c->stream);
+        return true;
+    });
+    return finish(c, FID_SIZER);
 }
 int caddy_debug_fid_block(caddy_ctx* c, int block, float* dst_nchw) {
     if (!fid_ctx_ok(c, "caddy_debug_fid_block")) return -2;
@@ -633,9 +599,9 @@ int caddy_debug_fid_block(caddy_ctx* c, int block, float* dst_nchw) {
     if (block == 3) hipLaunchKernelGGL(k_fid_d2f, dim3(grid_for((long)F->last_nf * FID_DIM)), dim3(256), 0, c->stream, (const double*)F->feat, dst_nchw, (long)F->last_nf * FID_DIM);
     else c->ck(pw_nhwc_to_nchw(F->taps[block], dst_nchw, (long)F->taps[block].C * F->taps[block].H * F->taps[block].W, 0, c->stream), "fid block");
     hipStreamSynchronize(c->stream);
-    return fid_finish(c);
+    return finish(c, FID_SIZER);
 }
-int caddy_debug_fid_fallback_layers(caddy_ctx* c) { return (c && c->fid) ? c->n_fallback : -1; }
+int caddy_debug_fid_fallback_layers(caddy_ctx* c) { return (c && c->kind == CTX_FID) ? c->n_fallback : -1; }
 /* on: the next chunks record events at the stage boundaries; ms5 (nullable) receives resize, stem, 35 x 35, 17 x 17 and 8 x 8 times of the LAST chunk */
 int caddy_debug_fid_stage_ms(caddy_ctx* c, int on, float* ms5) {
     if (!fid_ctx_ok(c, "caddy_debug_fid_stage_ms")) return -2;

@@ -1,10 +1,9 @@
-// Driver of the CADDY hot path: parameter table, layer construction, E / R / D / A graphs, tape-based BPTT.
+// Driver of the CADDY hot path: parameter table, layer construction, E / R / D / A graphs, tape-based BPTT, and the C ABI of the model context.
 // Reference behaviour: model/main_model/model.py (forward_full_model :84-286, generate_next :570-607) and the
 // reduced variant (model/reduced_model/rendering_network.py:30-42).  All device work goes through the kernels of
 // conv_mfma.hip / pointwise.hip / head.hip / pack.hip on one HIP stream; nothing here allocates device memory.
+// (The model-less contexts of the dataset evaluation are eval_ctx.cpp's.)
 #include "net.h"
-#include "frame_metrics.h"
-#include "detection.h"
 #include "fid.h"
 #include <cmath>
 #include <cstdio>
@@ -12,8 +11,8 @@
 #include <cstring>
 
 static thread_local std::string g_err;
-static int finish(caddy_ctx* c) {   // surface asynchronous launch errors of this API call
-    if (!c->dry && c->act.overflow() && !c->fail) { c->fail = true; g_err = "activation arena overflow (workspace smaller than caddy_workspace_bytes)"; }
+int finish(caddy_ctx* c, const char* sizer) {
+    if (!c->dry && c->act.overflow() && !c->fail) { c->fail = true; g_err = std::string("activation arena overflow (workspace smaller than ") + sizer + ")"; }
     if (!c->dry) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess && !c->fail) { c->fail = true; g_err = std::string("HIP error: ") + hipGetErrorString(e); }
@@ -1566,200 +1565,7 @@ static caddy_ctx* make_ctx(const caddy_config* cfg, float* params, float* grads,
     return c;
 }
 
-// Metrics context of the dataset evaluation (caddy_metrics_ctx_create): no model, the fused frame-metric pass's slab and result rows for max_frames frames, and with vgg the
-// packed VGG19 weights plus the activation arena of one chunk of the cosine similarity (vgg_metric_chunk's walk; grad_delta 0: nothing is back-propagated)
-static bool metrics_args_ok(int max_frames, int H, int W, int vgg) {
-    FmGeom g;
-    if (max_frames < 1 || H < 1 || W < 1) { set_error("caddy_metrics: max_frames, height and width must be positive"); return false; }
-    if (!fm_geometry(H, W, &g)) { set_error("caddy_metrics: frames smaller than the 11x11 SSIM window (after SSIM's down-sampling)"); return false; }
-    if (vgg && (H % 16 || W % 16)) { set_error("caddy_metrics: the VGG19 cosine similarity needs height and width multiples of 16 (four 2x2 max-pools)"); return false; }
-    return true;
-}
-static caddy_ctx* make_metrics_ctx(int max_frames, int H, int W, int vgg, void* ws, size_t act_cap) {
-    caddy_ctx* c = new caddy_ctx();
-    c->metrics_only = true; c->dry = ws == nullptr;
-    c->cfg.batch = max_frames; c->cfg.seq_len = 1; c->cfg.height = H; c->cfg.width = W; c->cfg.perceptual = vgg ? 1 : 0;
-    c->persist.base = (char*)ws; c->persist.cap = (size_t)-1;
-    if (vgg) vgg_build(c);
-    FmGeom g;
-    fm_geometry(H, W, &g);
-    c->sat_flag = (unsigned*)c->persist.alloc(sizeof(unsigned) * 2 * CADDY_N_FLAGS);
-    c->fm_slab = (double*)c->persist.alloc(sizeof(double) * FM_PART * (size_t)max_frames * g.tx * g.ty);
-    c->fm_out = (double*)c->persist.alloc(sizeof(double) * FM_SLOTS * (size_t)max_frames);
-    const size_t pbytes = (c->persist.high + 4095) & ~(size_t)4095;
-    c->act.base = (char*)ws + pbytes; c->act.cap = act_cap; c->grad_delta = 0;
-    c->act.reset();
-    return c;
-}
-static void metrics_sizes(int max_frames, int H, int W, int vgg, size_t* persist, size_t* act) {
-    caddy_ctx* c = make_metrics_ctx(max_frames, H, W, vgg, nullptr, (size_t)1 << 50);
-    if (vgg) vgg_metric_chunk(c, nullptr, nullptr, max_frames, 1.f, nullptr);
-    *persist = (c->persist.high + 4095) & ~(size_t)4095;
-    *act = ((c->act.high + 4095) & ~(size_t)4095) + 4096;
-    delete c;
-}
-
-// LPIPS context of the dataset evaluation (caddy_lpips_ctx_create; evaluation/metrics/lpips.py:14,33): a metrics context whose VGG state is the VGG16-to-relu5_3 trunk plus the five
-// lin vectors; the activation arena of one chunk of vgg_lpips_chunk's walk and 6 x max_frames result doubles
-#define LPIPS_ROWS 6
-static bool lpips_args_ok(int max_frames, int H, int W) {
-    if (max_frames < 1 || H < 1 || W < 1) { set_error("caddy_lpips: max_frames, height and width must be positive"); return false; }
-    if (H % 16 || W % 16) { set_error("caddy_lpips: LPIPS (VGG16) needs height and width multiples of 16 (four 2x2 max-pools)"); return false; }
-    return true;
-}
-static caddy_ctx* make_lpips_ctx(int max_frames, int H, int W, void* ws, size_t act_cap) {
-    caddy_ctx* c = new caddy_ctx();
-    c->metrics_only = true; c->dry = ws == nullptr;
-    c->cfg.batch = max_frames; c->cfg.seq_len = 1; c->cfg.height = H; c->cfg.width = W; c->cfg.perceptual = 1;
-    c->persist.base = (char*)ws; c->persist.cap = (size_t)-1;
-    vgg_build(c, VGG_KIND_LPIPS);
-    c->sat_flag = (unsigned*)c->persist.alloc(sizeof(unsigned) * 2 * CADDY_N_FLAGS);
-    c->fm_out = (double*)c->persist.alloc(sizeof(double) * FM_SLOTS * (size_t)max_frames);      // (FM_SLOTS >= LPIPS_ROWS rows: caddy_platform_positions keeps working on it)
-    const size_t pbytes = (c->persist.high + 4095) & ~(size_t)4095;
-    c->act.base = (char*)ws + pbytes; c->act.cap = act_cap; c->grad_delta = 0;
-    c->act.reset();
-    return c;
-}
-static void lpips_sizes(int max_frames, int H, int W, size_t* persist, size_t* act) {
-    caddy_ctx* c = make_lpips_ctx(max_frames, H, W, nullptr, (size_t)1 << 50);
-    vgg_lpips_chunk(c, nullptr, nullptr, max_frames, 1.f, nullptr, max_frames);
-    *persist = (c->persist.high + 4095) & ~(size_t)4095;
-    *act = ((c->act.high + 4095) & ~(size_t)4095) + 4096;
-    delete c;
-}
-
 extern "C" {
-size_t caddy_lpips_workspace_bytes(int max_frames, int height, int width) {
-    if (!lpips_args_ok(max_frames, height, width)) return 0;
-    size_t p, a; lpips_sizes(max_frames, height, width, &p, &a);
-    return p + a + 4096;
-}
-caddy_ctx* caddy_lpips_ctx_create(int max_frames, int height, int width, void* workspace, size_t bytes) {
-    if (!lpips_args_ok(max_frames, height, width)) return nullptr;
-    if (!workspace) { set_error("null buffer"); return nullptr; }
-    if ((uintptr_t)workspace & 255) { set_error("the workspace must be 256-byte aligned"); return nullptr; }
-    size_t p, a; lpips_sizes(max_frames, height, width, &p, &a);
-    if (bytes < p + a) { set_error("workspace too small (see caddy_lpips_workspace_bytes)"); return nullptr; }
-    caddy_ctx* c = make_lpips_ctx(max_frames, height, width, workspace, a);
-    hipMemset(c->sat_flag, 0, sizeof(unsigned) * 2 * CADDY_N_FLAGS);
-    if (const char* e = getenv("CADDY_VGG_S16")) c->vgg_s16 = atoi(e) != 0;
-    if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) c->vgg_precision = c->vgg_precision_bwd = PREC_FP32;
-    return c;
-}
-int caddy_lpips_param_count(void) { return lpips_param_count(); }
-int caddy_lpips_param_info_get(int index, caddy_param_info* out) { return lpips_param_info(index, out); }
-long caddy_lpips_param_floats(void) { return lpips_param_floats(); }
-int caddy_load_lpips(caddy_ctx* c, const float* lpips_flat) {
-    if (!c || !c->metrics_only || c->vgg.kind != VGG_KIND_LPIPS) { set_error("caddy_load_lpips needs a context from caddy_lpips_ctx_create"); return -2; }
-    c->fail = false;
-    if (!lpips_flat) { set_error("null input"); return -2; }
-    return vgg_load(c, lpips_flat);
-}
-int caddy_debug_lpips_tap_formats(caddy_ctx* c) { return (c && c->vgg.kind == VGG_KIND_LPIPS) ? (int)c->vgg.tap_s16 : -1; }
-int caddy_frame_lpips(caddy_ctx* c, const float* ref, const float* gen, int B, int T, float value_range, double* out_host) {
-    if (!c || !c->metrics_only || c->vgg.kind != VGG_KIND_LPIPS) { set_error("caddy_frame_lpips needs a context from caddy_lpips_ctx_create"); return -2; }
-    c->fail = false;
-    if (!ref || !gen || !out_host) { set_error("null input"); return -2; }
-    if (B < 1 || T < 1 || !(value_range > 0.f)) { set_error("caddy_frame_lpips: B, T and value_range must be positive"); return -2; }
-    if (!c->vgg.loaded) { set_error("caddy_frame_lpips: no LPIPS weights were loaded (caddy_load_lpips)"); return -2; }
-    const int M = c->cfg.batch;
-    const long N = (long)B * T, fr = 3L * c->cfg.height * c->cfg.width;
-    hipStream_t st = c->stream;
-    std::vector<double> tmp((size_t)LPIPS_ROWS * M);
-    c->vgg.tap_s16 = 0;
-    for (long n0 = 0; n0 < N; n0 += M) {      // chunks of max_frames frames (the arena of the VGG16 trunk)
-        const int nf = (int)std::min<long>(M, N - n0);
-        for (int attempt = 0; attempt < 2; attempt++) {
-            // f16 range guard of the split-f16 forward, as in caddy_frame_metrics: a layer that met |x| > 65504 moves to split bf16 for good and the chunk runs again
-            if (vgg_lpips_chunk(c, ref + n0 * fr, gen + n0 * fr, nf, value_range, c->fm_out, M) != 0) return finish(c);
-            unsigned v[VGG_NCONV];
-            hipMemcpyAsync(v, c->sat_flag + CADDY_VGG_FLAG0, sizeof(v), hipMemcpyDeviceToHost, st);
-            hipStreamSynchronize(st);
-            bool again = false;
-            for (int i = 0; i < VGG_NCONV; i++) if (v[i] && !c->layer_fallback[CADDY_VGG_FLAG0 + i]) { c->layer_fallback[CADDY_VGG_FLAG0 + i] = true; c->n_fallback++; again = true; }
-            if (!again) break;
-            hipMemsetAsync(c->sat_flag, 0, sizeof(unsigned) * 2 * CADDY_N_FLAGS, st);
-        }
-        hipMemcpyAsync(tmp.data(), c->fm_out, sizeof(double) * LPIPS_ROWS * M, hipMemcpyDeviceToHost, st);
-        hipStreamSynchronize(st);
-        for (int s = 0; s < LPIPS_ROWS; s++)
-            for (int j = 0; j < nf; j++) out_host[s * N + n0 + j] = tmp[(size_t)s * M + j];
-    }
-    return finish(c);
-}
-size_t caddy_metrics_workspace_bytes(int max_frames, int height, int width, int vgg) {
-    if (!metrics_args_ok(max_frames, height, width, vgg)) return 0;
-    size_t p, a; metrics_sizes(max_frames, height, width, vgg, &p, &a);
-    return p + a + 4096;
-}
-caddy_ctx* caddy_metrics_ctx_create(int max_frames, int height, int width, int vgg, void* workspace, size_t bytes) {
-    if (!metrics_args_ok(max_frames, height, width, vgg)) return nullptr;
-    if (!workspace) { set_error("null buffer"); return nullptr; }
-    if ((uintptr_t)workspace & 255) { set_error("the workspace must be 256-byte aligned"); return nullptr; }
-    size_t p, a; metrics_sizes(max_frames, height, width, vgg, &p, &a);
-    if (bytes < p + a) { set_error("workspace too small (see caddy_metrics_workspace_bytes)"); return nullptr; }
-    caddy_ctx* c = make_metrics_ctx(max_frames, height, width, vgg, workspace, a);
-    hipMemset(c->sat_flag, 0, sizeof(unsigned) * 2 * CADDY_N_FLAGS);
-    if (const char* e = getenv("CADDY_VGG_S16")) c->vgg_s16 = atoi(e) != 0;
-    if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) c->vgg_precision = c->vgg_precision_bwd = PREC_FP32;
-    return c;
-}
-int caddy_frame_metrics(caddy_ctx* c, const float* ref, const float* gen, int B, int T, float value_range, int want_vgg, double* out_host) {
-    if (!c || !c->metrics_only || c->vgg.kind != VGG_KIND_VGG19) { set_error("caddy_frame_metrics needs a context from caddy_metrics_ctx_create"); return -2; }
-    c->fail = false;
-    if (!ref || !gen || !out_host) { set_error("null input"); return -2; }
-    if (B < 1 || T < 1 || !(value_range > 0.f)) { set_error("caddy_frame_metrics: B, T and value_range must be positive"); return -2; }
-    if (want_vgg && !(c->cfg.perceptual && c->vgg.loaded)) { set_error("caddy_frame_metrics: want_vgg needs a context created with vgg = 1 and loaded VGG19 weights (caddy_load_vgg)"); return -2; }
-    FmGeom g;
-    if (!fm_geometry(c->cfg.height, c->cfg.width, &g)) { set_error("caddy_metrics: frames smaller than the 11x11 SSIM window (after SSIM's down-sampling)"); return -2; }
-    const int M = c->cfg.batch;
-    const long N = (long)B * T, fr = 3L * c->cfg.height * c->cfg.width;
-    hipStream_t st = c->stream;
-    std::vector<double> tmp((size_t)FM_SLOTS * M);
-    for (long n0 = 0; n0 < N; n0 += M) {      // chunks of max_frames frames (the slab of the fused pass, the arena of the VGG19 branch)
-        const int nf = (int)std::min<long>(M, N - n0);
-        c->ck(fm_launch(ref, gen, (int)n0, nf, T, g, value_range, c->fm_slab, c->fm_out, M, st), "frame metrics");
-        for (int attempt = 0; want_vgg && attempt < 2; attempt++) {
-            // f16 range guard of the split-f16 VGG19 forward: a layer that met |x| > 65504 moves to split bf16 for good (as caddy_f16_saturated does) and the chunk runs again
-            if (vgg_metric_chunk(c, ref + n0 * fr, gen + n0 * fr, nf, value_range, c->fm_out + (size_t)CADDY_FM_VGG_SIM * M) != 0) return finish(c);
-            unsigned v[VGG_NCONV];
-            hipMemcpyAsync(v, c->sat_flag + CADDY_VGG_FLAG0, sizeof(v), hipMemcpyDeviceToHost, st);
-            hipStreamSynchronize(st);
-            bool again = false;
-            for (int i = 0; i < VGG_NCONV; i++) if (v[i] && !c->layer_fallback[CADDY_VGG_FLAG0 + i]) { c->layer_fallback[CADDY_VGG_FLAG0 + i] = true; c->n_fallback++; again = true; }
-            if (!again) break;
-            hipMemsetAsync(c->sat_flag, 0, sizeof(unsigned) * 2 * CADDY_N_FLAGS, st);
-        }
-        hipMemcpyAsync(tmp.data(), c->fm_out, sizeof(double) * FM_SLOTS * M, hipMemcpyDeviceToHost, st);
-        hipStreamSynchronize(st);
-        for (int s = 0; s < FM_SLOTS; s++)
-            for (int j = 0; j < nf; j++) out_host[s * N + n0 + j] = (s == CADDY_FM_VGG_SIM && !want_vgg) ? NAN : tmp[(size_t)s * M + j];
-    }
-    return finish(c);
-}
-
-int caddy_platform_positions(caddy_ctx* c, const float* obs, int B, int T, int row, float lo, float hi, int min_run, int* out_host) {
-    if (!c || !c->metrics_only || c->fid) { set_error("caddy_platform_positions needs a context from caddy_metrics_ctx_create"); return -2; }
-    c->fail = false;
-    if (!obs || !out_host) { set_error("null input"); return -2; }
-    const int H = c->cfg.height, W = c->cfg.width;
-    if (B < 1 || T < 1) { set_error("caddy_platform_positions: B and T must be positive"); return -2; }
-    if (row < 0 || row >= H) { set_error("caddy_platform_positions: row outside the frame (0 <= row < height)"); return -2; }
-    if (min_run < 1) { set_error("caddy_platform_positions: min_run must be positive"); return -2; }
-    if (W > DET_MAX_W) { set_error("caddy_platform_positions: frames wider than 4096 columns"); return -2; }
-    const int M = c->cfg.batch;
-    const long N = (long)B * T;
-    hipStream_t st = c->stream;
-    int* dev = (int*)c->fm_out;      // (FM_SLOTS doubles = 72 bytes per frame: room for one int32 each)
-    for (long n0 = 0; n0 < N; n0 += M) {      // chunks of max_frames frames, as caddy_frame_metrics
-        const int nf = (int)std::min<long>(M, N - n0);
-        c->ck(det_platform_launch(obs, (int)n0, nf, H, W, row, lo, hi, min_run, dev, st), "platform positions");
-        hipMemcpyAsync(out_host + n0, dev, sizeof(int) * nf, hipMemcpyDeviceToHost, st);
-        hipStreamSynchronize(st);
-    }
-    return finish(c);
-}
-
 int caddy_param_count(const caddy_config* cfg) {
     if (!check_cfg(cfg)) return -1;
     std::vector<ParamEntry> t; long a, b; build_param_table(*cfg, t, &a, &b); return (int)t.size();
@@ -1844,13 +1650,13 @@ int caddy_set_allreduce_hook(caddy_ctx* c, void (*hook)(float*, int, void*), voi
     return 0;
 }
 int caddy_forward_full(caddy_ctx* c, const float* obs, int gt_init, float tau, const caddy_noise* noise, int training, const float* samples_in, const float* variations_in) {
-    if (c->metrics_only) { set_error("a metrics context (caddy_metrics_ctx_create) holds no model"); return -2; }
+    if (!ctx_needs(c, CTX_MODEL, "caddy_forward_full")) return -2;
     c->fail = false;
     if (!obs || !noise) { set_error("null input"); return -2; }
     return forward_full(c, obs, gt_init, tau, noise, training, samples_in, variations_in);
 }
 int caddy_forward_pretraining(caddy_ctx* c, const float* obs, float tau, const caddy_noise* noise, int training, const float* samples_in, const float* variations_in) {
-    if (c->metrics_only) { set_error("a metrics context (caddy_metrics_ctx_create) holds no model"); return -2; }
+    if (!ctx_needs(c, CTX_MODEL, "caddy_forward_pretraining")) return -2;
     c->fail = false;
     if (!obs || !noise) { set_error("null input"); return -2; }
     return forward_pretraining(c, obs, tau, noise, training, samples_in, variations_in);
@@ -1863,7 +1669,7 @@ int caddy_set_action_member(caddy_ctx* c, int member) {
     c->member = member; return 0;
 }
 int caddy_adam_step_ex(caddy_ctx* c, float* m, float* v, float lr, float b1, float b2, float eps, float wd, int step, const int* member_step, int s2h_step, float gscale) {
-    if (c->metrics_only) { set_error("a metrics context (caddy_metrics_ctx_create) holds no model"); return -2; }
+    if (!ctx_needs(c, CTX_MODEL, "caddy_adam_step_ex")) return -2;
     // torch.optim.Adam keeps `step` per parameter and skips parameters whose .grad is None -- no moment update, no weight decay.  Which parameters those are depends on
     // optimizer.zero_grad(): set_to_none (torch >= 2.0 default) leaves every parameter that the last backward did not reach without a gradient; the zero-filling form of
     // torch < 2.0 (the reference pins pytorch 1.4.0, env.yml) keeps a ZERO gradient on every parameter that has had one before, so Adam goes on ageing its moments and applying
@@ -1897,7 +1703,7 @@ long caddy_vgg_param_floats(void) { return vgg_param_floats(); }
 int caddy_load_vgg(caddy_ctx* c, const float* vgg_flat) {
     c->fail = false;
     if (!vgg_flat) { set_error("null input"); return -2; }
-    if (c->vgg.kind != VGG_KIND_VGG19) { set_error("caddy_load_vgg: the context is an LPIPS context (use caddy_load_lpips)"); return -2; }
+    if (c->kind & (CTX_LPIPS | CTX_FID)) { set_error("caddy_load_vgg: the context is an LPIPS context (use caddy_load_lpips)"); return -2; }
     return vgg_load(c, vgg_flat);
 }
 int caddy_set_perceptual_prefetch(caddy_ctx* c, int on) { c->perc_prefetch = on != 0; return 0; }
@@ -1938,7 +1744,7 @@ int caddy_set_precision(caddy_ctx* c, int forward, int backward) {
     c->prec_fwd = forward; c->prec_bwd = backward; return 0;
 }
 int caddy_start_inference(caddy_ctx* c) {
-    if (c->metrics_only) { set_error("a metrics context (caddy_metrics_ctx_create) holds no model"); return -2; }
+    if (!ctx_needs(c, CTX_MODEL, "caddy_start_inference")) return -2;
     c->fail = false; return start_inference(c);
 }
 // Poll of the per-layer f16 range guards: waits for the stream, reads and clears the flag words.  Returns bit 0: a split-f16 forward convolution (model or VGG19) staged |x| > 65504
@@ -1961,7 +1767,7 @@ int caddy_f16_saturated(caddy_ctx* c) {
 }
 int caddy_fallback_layers(caddy_ctx* c) { return c->n_fallback; }
 int caddy_generate_next(caddy_ctx* c, const float* observation, int action, const float* variation, float* frame_out, float* obs_out) {
-    if (c->metrics_only) { set_error("a metrics context (caddy_metrics_ctx_create) holds no model"); return -2; }
+    if (!ctx_needs(c, CTX_MODEL, "caddy_generate_next")) return -2;
     c->fail = false;
     if (!observation || !frame_out) { set_error("null input"); return -2; }
     {   // the boundary kernel behind the frame reads `observation` while it writes obs_out = cat[frame, observation[:-3]] and frame_out: the buffers must not overlap

@@ -62,6 +62,12 @@ struct Arena {
     bool overflow() const { return off > top; }
 };
 
+// Kind of a context, one bit each: an entry point names the kinds it serves (ctx_needs)
+enum { CTX_MODEL = 1,       // caddy_ctx_create
+       CTX_METRICS = 2,     // caddy_metrics_ctx_create
+       CTX_LPIPS = 4,       // caddy_lpips_ctx_create
+       CTX_FID = 8 };       // caddy_fid_ctx_create
+
 struct BNL;
 #define CADDY_N_FLAGS 128
 #define CADDY_VGG_FLAG0 96
@@ -237,8 +243,9 @@ struct caddy_ctx {
     bool seeds_only = false;         // caddy_debug_set_seeds_only: caddy_loss_backward stops after the loss kernels (tests of the loss gradient seeds)
     bool poison_nz = false;          // caddy_debug_set_poison: NaN-fill the first-touch gradient region before every backward (tests)
     int hs, ws;   // state resolution
-    // dataset evaluation (caddy_metrics_ctx_create): a context without a model -- the fused frame-metric pass (frame_metrics.hip) and, with VGG19 weights, the cosine similarity
-    bool metrics_only = false;
+    // what the context was created for (CTX_*): the model, or one of the model-less contexts of the dataset evaluation (eval_ctx.cpp) -- the fused frame-metric pass
+    // (frame_metrics.hip) with the VGG19 cosine similarity, LPIPS, the FID feature network
+    int kind = CTX_MODEL;
     double* fm_slab = nullptr;       // per (frame, tile) partials of the fused pass (cfg.batch = max_frames frames)
     double* fm_out = nullptr;        // CADDY_FM_COUNT x max_frames results of the current chunk
     struct FidState* fid = nullptr;  // FID feature network (caddy_fid_ctx_create; fid.hip owns it)
@@ -326,4 +333,7 @@ struct caddy_ctx {
 
 void build_param_table(const caddy_config& c, std::vector<ParamEntry>& t, long* n_floats, long* n_train);
 void set_error(const std::string& s);
+int finish(caddy_ctx* c, const char* sizer = "caddy_workspace_bytes");      // end of an API call: surfaces an arena overflow (workspace smaller than `sizer` asks for) and asynchronous launch errors
+// false + caddy_last_error unless c is a context of one of `kinds` (CTX_* bits): "`who` needs a context from caddy_*_ctx_create", or that a metrics context holds no model
+bool ctx_needs(caddy_ctx* c, int kinds, const char* who);
 bool caddy_serial_streams();      // CADDY_STREAMS=0 (net.cpp)

@@ -10,8 +10,7 @@ struct VggLayer { PackDesc pd; float* wp; float* wpd; float* bias; int kd, cd_pa
 // The trunk a context runs: (torchvision features index, Cin, Cout) of its 13 convolutions; pool_before: MaxPool2d(2, 2) on the input; tap: feature level this conv's ReLU is, or -1
 struct VggSpec { int idx, cin, cout, pool_before, tap; };
 enum { VGG_KIND_VGG19 = 0,        // vgg19().features up to relu5_1, taps relu{1..5}_1 (model/layers/vgg.py:25-34): perceptual loss, VGG cosine similarity
-       VGG_KIND_LPIPS = 1,
-       VGG_KIND_FID = 2 };        // no VGG at all: the context of caddy_fid_ctx_create (fid.hip), refused by every VGG / frame-metric entry point      // vgg16().features up to relu5_3, taps relu1_2, 2_2, 3_3, 4_3, 5_3: the trunk of lpips.LPIPS(net='vgg') (evaluation/metrics/lpips.py:14)
+       VGG_KIND_LPIPS = 1 };      // vgg16().features up to relu5_3, taps relu1_2, 2_2, 3_3, 4_3, 5_3: the trunk of lpips.LPIPS(net='vgg') (evaluation/metrics/lpips.py:14)
 const VggSpec* vgg_spec_table(int kind);
 struct VggState { bool enabled = false, loaded = false; int kind = VGG_KIND_VGG19; const VggSpec* spec = nullptr; VggLayer conv[VGG_NCONV];
                   float* lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // LPIPS: the per-channel weights of lin{l}.model[1] (C_l floats each)

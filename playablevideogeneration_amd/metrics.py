@@ -39,7 +39,7 @@ def psnr(reference_observations: torch.Tensor, generated_observations: torch.Ten
 SLOTS = ("mse", "motion_masked_mse", "psnr", "ssim", "vgg_sim", "ref_min", "ref_max", "gen_min", "gen_max")      # CADDY_FM_* of include/caddy_hip.h
 VGG_FRAMES_256 = 30      # frames per VGG19 chunk at 256 x 256 (scaled by the frame area): ~4 GB of feature maps
 _default_lib = None
-_contexts: Dict = {}
+_contexts: Dict = {}      # every cached context: (kind, library, device, geometry, weights) -> FrameMetrics | LPIPS | InceptionFeatures
 
 
 def set_library(lib) -> None:
@@ -47,8 +47,6 @@ def set_library(lib) -> None:
     global _default_lib
     _default_lib = lib
     _contexts.clear()
-    _lpips_contexts.clear()
-    _fid_contexts.clear()
 
 
 def _bind(lib):
@@ -88,45 +86,66 @@ def _bind(lib):
     return lib
 
 
-class FrameMetrics:
-    """A metrics context for frames of height x width: the fused per-frame pass and, with `vgg_state_dict` (torchvision vgg19 naming, as
-    Engine.load_vgg takes it), the VGG19 cosine similarity.  Calls with more than `max_frames` frames run in chunks of `max_frames`."""
+def _param_table(count, info_get):
+    """[(name, offset, shape)] of a caddy_*_param_count / caddy_*_param_info_get pair"""
+    from .engine import ParamInfo
+    info, table = ParamInfo(), []
+    for i in range(count()):
+        info_get(i, C.byref(info))
+        table.append((info.name.decode(), int(info.offset), tuple(info.shape[:info.ndim])))
+    return table
 
-    def __init__(self, height: int, width: int, max_frames: int, vgg_state_dict=None, lib=None, device=None):
+
+def _cached(key, weights, make, stale=lambda ctx: False):
+    """the context cached under `key`, made (again, if `stale`) by `make`; `weights` is kept alive because the key holds its id"""
+    ctx = _contexts.get(key)
+    if ctx is None or stale(ctx):
+        _contexts.pop(key, None)
+        ctx = make()
+        ctx._keep = weights
+        _contexts[key] = ctx
+    return ctx
+
+
+class _EvalContext:
+    """What the evaluation contexts share: library and device, a context created in a workspace of its own, error handling and the upload of a flat parameter buffer."""
+
+    def __init__(self, height: int, width: int, max_frames: int, lib, device):
         from . import _lib
-        from .engine import CaddyError
         self.lib = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
         kind = getattr(self.lib, "_caddy_device_type", "cuda")
         self.device = torch.device(device) if device is not None else torch.device(kind)
-        self.H, self.W, self.max_frames, self.vgg = int(height), int(width), int(max_frames), vgg_state_dict is not None
+        self.H, self.W, self.max_frames = int(height), int(width), int(max_frames)
         self._err = lambda: self.lib.caddy_last_error().decode()
-        n = self.lib.caddy_metrics_workspace_bytes(self.max_frames, self.H, self.W, int(self.vgg))
+
+    def _create(self, workspace_bytes, ctx_create, *extra):
+        """workspace_bytes / ctx_create: the kind's two C functions, both taking (max_frames, height, width, *extra)"""
+        from .engine import CaddyError
+        n = workspace_bytes(self.max_frames, self.H, self.W, *extra)
         if n == 0:
             raise CaddyError(self._err())
         raw = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
         self._ws = raw
         self.ws_bytes = n
-        self.ctx = self.lib.caddy_metrics_ctx_create(self.max_frames, self.H, self.W, int(self.vgg), raw.data_ptr() + (-raw.data_ptr()) % 256, n)
+        self.ctx = ctx_create(self.max_frames, self.H, self.W, *extra, raw.data_ptr() + (-raw.data_ptr()) % 256, n)
         if not self.ctx:
             raise CaddyError(self._err())
-        if self.vgg:
-            from .engine import ParamInfo
-            info = ParamInfo()
-            flat = torch.zeros(self.lib.caddy_vgg_param_floats(), dtype=torch.float32, device=self.device)
-            for i in range(self.lib.caddy_vgg_param_count()):
-                self.lib.caddy_vgg_param_info_get(i, C.byref(info))
-                name, off, shape = info.name.decode(), info.offset, tuple(info.shape[:info.ndim])
-                key = name if name in vgg_state_dict else name[len("features."):]
-                if key not in vgg_state_dict:
-                    raise CaddyError(f"VGG19 state dict lacks {name}")
-                t = vgg_state_dict[key].detach().to(self.device, torch.float32)
-                if tuple(t.shape) != shape:
-                    raise CaddyError(f"VGG19 {name}: shape {tuple(t.shape)}, expected {shape}")
-                flat[off:off + t.numel()] = t.reshape(-1)
-            self._stream()
-            self._check(self.lib.caddy_load_vgg(self.ctx, flat.data_ptr()))
-            if self.device.type == "cuda":
-                torch.cuda.current_stream(self.device).synchronize()
+
+    def _load(self, load, floats, table, state, what, staging=None):
+        """fills a flat fp32 buffer of `floats` floats with the tensors of `state` along the (name, offset, shape) `table` -- on `staging`, by default the context's
+        device -- and hands it to the C function `load`"""
+        from .engine import CaddyError
+        flat = torch.zeros(floats, dtype=torch.float32, device=self.device if staging is None else staging)
+        for name, off, shape in table:
+            t = state[name].detach().to(flat.device, torch.float32)
+            if tuple(t.shape) != shape:
+                raise CaddyError(f"{what} {name}: shape {tuple(t.shape)}, expected {shape}")
+            flat[off:off + t.numel()] = t.reshape(-1)
+        flat = flat.to(self.device)
+        self._stream()
+        self._check(load(self.ctx, flat.data_ptr()))
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()
 
     def _check(self, rc):
         if rc != 0:
@@ -136,9 +155,39 @@ class FrameMetrics:
     def _stream(self):
         self.lib.caddy_set_stream(self.ctx, torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0)
 
+    def __del__(self):
+        if getattr(self, "ctx", None):
+            if self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).synchronize()
+            self.lib.caddy_ctx_destroy(self.ctx)
+            self.ctx = None
+
+
+class _VggContext(_EvalContext):
+    """the two kinds that run a VGG trunk"""
+
     def set_vgg_precision(self, forward: int):
-        """arithmetic of the VGG19 convolutions: 0 (exact fp32) | 16 (split f16, default) | 18 (plain f16)"""
+        """arithmetic of the VGG convolutions: 0 (exact fp32) | 16 (split f16, default) | 18 (plain f16)"""
         self._check(self.lib.caddy_set_vgg_precision(self.ctx, int(forward), 17))
+
+
+class FrameMetrics(_VggContext):
+    """A metrics context for frames of height x width: the fused per-frame pass and, with `vgg_state_dict` (torchvision vgg19 naming, as
+    Engine.load_vgg takes it), the VGG19 cosine similarity.  Calls with more than `max_frames` frames run in chunks of `max_frames`."""
+
+    def __init__(self, height: int, width: int, max_frames: int, vgg_state_dict=None, lib=None, device=None):
+        super().__init__(height, width, max_frames, lib, device)
+        self.vgg = vgg_state_dict is not None
+        self._create(self.lib.caddy_metrics_workspace_bytes, self.lib.caddy_metrics_ctx_create, int(self.vgg))
+        if self.vgg:
+            from .engine import CaddyError
+            table, state = _param_table(self.lib.caddy_vgg_param_count, self.lib.caddy_vgg_param_info_get), {}
+            for name, _, _ in table:      # torchvision's vgg19() names, or those of its .features
+                key = name if name in vgg_state_dict else name[len("features."):]
+                if key not in vgg_state_dict:
+                    raise CaddyError(f"VGG19 state dict lacks {name}")
+                state[name] = vgg_state_dict[key]
+            self._load(self.lib.caddy_load_vgg, self.lib.caddy_vgg_param_floats(), table, state, "VGG19")
 
     def __call__(self, reference_observations: torch.Tensor, generated_observations: torch.Tensor, value_range: float = 1.0,
                  want_vgg: bool = False) -> Dict[str, torch.Tensor]:
@@ -170,13 +219,6 @@ class FrameMetrics:
                                                       out.ctypes.data_as(C.c_void_p)))
         return out.astype(np.int64)
 
-    def __del__(self):
-        if getattr(self, "ctx", None):
-            if self.device.type == "cuda":
-                torch.cuda.current_stream(self.device).synchronize()
-            self.lib.caddy_ctx_destroy(self.ctx)
-            self.ctx = None
-
 
 def check_range(values: Dict[str, torch.Tensor], which: str = "ref") -> None:
     """DatasetEvaluator.check_range (evaluation/dataset_evaluator.py:73-83) from the per-frame minima / maxima of the fused pass"""
@@ -191,15 +233,10 @@ def _cached_context(observations: torch.Tensor, vgg_state_dict, lib) -> FrameMet
     n = int(B) * int(T)
     lib = lib if lib is not None else _default_lib
     vkey = None if vgg_state_dict is None else id(vgg_state_dict)
-    key = (id(lib), str(observations.device), int(H), int(W), vkey)
-    fm = _contexts.get(key)
+    key = ("metrics", id(lib), str(observations.device), int(H), int(W), vkey)
     want = n if vgg_state_dict is None else min(n, max(1, VGG_FRAMES_256 * 256 * 256 // (int(H) * int(W))))
-    if fm is None or (vgg_state_dict is None and fm.max_frames < min(n, 1024)):
-        _contexts.pop(key, None)
-        fm = FrameMetrics(H, W, min(want, 1024), vgg_state_dict, lib)
-        fm._keep = vgg_state_dict      # (the cache key holds its id)
-        _contexts[key] = fm
-    return fm
+    return _cached(key, vgg_state_dict, lambda: FrameMetrics(H, W, min(want, 1024), vgg_state_dict, lib),
+                   lambda fm: vgg_state_dict is None and fm.max_frames < min(n, 1024))
 
 
 def frame_metrics(reference_observations: torch.Tensor, generated_observations: torch.Tensor, value_range: float = 1.0, vgg_state_dict=None,
@@ -256,7 +293,6 @@ LPIPS_FRAMES_256 = 30      # frames per VGG16 chunk at 256 x 256 (scaled by the 
 LPIPS_CONVS = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)      # torchvision vgg16().features indices of the trunk's convolutions
 LPIPS_LEVELS = ("relu1_2", "relu2_2", "relu3_3", "relu4_3", "relu5_3")
 LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)      # the package's scaling layer; compiled into csrc/lpips.hip
-_lpips_contexts: Dict = {}
 
 
 def lpips_state(weights: Dict[str, torch.Tensor], linear: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
@@ -313,46 +349,16 @@ def find_lpips_weights(cfg) -> Optional[Dict[str, torch.Tensor]]:
     return None
 
 
-class LPIPS:
+class LPIPS(_VggContext):
     """An LPIPS context for frames of height x width (multiples of 16) with the weights of lpips_state().  Calls with more than `max_frames` frames run in chunks."""
 
     def __init__(self, height: int, width: int, max_frames: int, lpips_weights, lib=None, device=None):
-        from . import _lib
-        from .engine import CaddyError, ParamInfo
-        self.lib = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
-        kind = getattr(self.lib, "_caddy_device_type", "cuda")
-        self.device = torch.device(device) if device is not None else torch.device(kind)
-        self.H, self.W, self.max_frames = int(height), int(width), int(max_frames)
-        self._err = lambda: self.lib.caddy_last_error().decode()
+        super().__init__(height, width, max_frames, lib, device)
         state = lpips_state(lpips_weights)
-        n = self.lib.caddy_lpips_workspace_bytes(self.max_frames, self.H, self.W)
-        if n == 0:
-            raise CaddyError(self._err())
-        raw = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-        self._ws = raw
-        self.ws_bytes = n
-        self.ctx = self.lib.caddy_lpips_ctx_create(self.max_frames, self.H, self.W, raw.data_ptr() + (-raw.data_ptr()) % 256, n)
-        if not self.ctx:
-            raise CaddyError(self._err())
-        info = ParamInfo()
-        flat = torch.zeros(self.lib.caddy_lpips_param_floats(), dtype=torch.float32, device=self.device)
-        for i in range(self.lib.caddy_lpips_param_count()):
-            self.lib.caddy_lpips_param_info_get(i, C.byref(info))
-            name, off, shape = info.name.decode(), info.offset, tuple(info.shape[:info.ndim])
-            t = state[name].detach().to(self.device, torch.float32)
-            if tuple(t.shape) != shape:
-                raise CaddyError(f"LPIPS {name}: shape {tuple(t.shape)}, expected {shape}")
-            flat[off:off + t.numel()] = t.reshape(-1)
-        self._stream()
-        self._check(self.lib.caddy_load_lpips(self.ctx, flat.data_ptr()))
-        if self.device.type == "cuda":
-            torch.cuda.current_stream(self.device).synchronize()
+        self._create(self.lib.caddy_lpips_workspace_bytes, self.lib.caddy_lpips_ctx_create)
+        self._load(self.lib.caddy_load_lpips, self.lib.caddy_lpips_param_floats(), _param_table(self.lib.caddy_lpips_param_count, self.lib.caddy_lpips_param_info_get),
+                   state, "LPIPS")
         self.levels = None
-
-    _check = FrameMetrics._check
-    _stream = FrameMetrics._stream
-    set_vgg_precision = FrameMetrics.set_vgg_precision
-    __del__ = FrameMetrics.__del__
 
     def tap_formats(self) -> int:
         """bit l set: the level-l feature maps travelled as S16 tensors in some chunk of the last call (caddy_debug_lpips_tap_formats)"""
@@ -377,14 +383,9 @@ def _cached_lpips(observations: torch.Tensor, lpips_weights, lib) -> LPIPS:
     """the LPIPS context of this library, device, frame geometry and weights (cached like _cached_context)"""
     B, T, _, H, W = observations.shape
     lib = lib if lib is not None else _default_lib
-    key = (id(lib), str(observations.device), int(H), int(W), id(lpips_weights))
-    ctx = _lpips_contexts.get(key)
-    if ctx is None:
-        want = min(int(B) * int(T), max(1, LPIPS_FRAMES_256 * 256 * 256 // (int(H) * int(W))))
-        ctx = LPIPS(H, W, min(want, 1024), lpips_weights, lib)
-        ctx._keep = lpips_weights      # (the cache key holds its id)
-        _lpips_contexts[key] = ctx
-    return ctx
+    key = ("lpips", id(lib), str(observations.device), int(H), int(W), id(lpips_weights))
+    want = min(int(B) * int(T), max(1, LPIPS_FRAMES_256 * 256 * 256 // (int(H) * int(W))))
+    return _cached(key, lpips_weights, lambda: LPIPS(H, W, min(want, 1024), lpips_weights, lib))
 
 
 def lpips(reference_observations: torch.Tensor, generated_observations: torch.Tensor, lpips_weights, value_range: float = 1.0, lib=None,
@@ -399,7 +400,6 @@ def lpips(reference_observations: torch.Tensor, generated_observations: torch.Te
 FID_FRAMES_256 = 64       # frames per Inception chunk at 256 x 256 with the 299 x 299 resize: ~0.9 GB of activations
 FID_DIM = 2048
 FID_BLOCK_CHANNELS = (64, 192, 768, 2048)      # InceptionV3.BLOCK_INDEX_BY_DIM (pytorch_fid/inception.py:24-29)
-_fid_contexts: Dict = {}
 _fid_names = None
 
 
@@ -407,13 +407,9 @@ def fid_param_table(lib=None):
     """[(name, offset, shape)] of caddy_fid_param_info_get: the trunk's tensors under the pt_inception-2015-12-05 names, in graph order"""
     global _fid_names
     from . import _lib
-    from .engine import ParamInfo
     if _fid_names is None or lib is not None:
         L = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
-        info, table = ParamInfo(), []
-        for i in range(L.caddy_fid_param_count()):
-            L.caddy_fid_param_info_get(i, C.byref(info))
-            table.append((info.name.decode(), int(info.offset), tuple(info.shape[:info.ndim])))
+        table = _param_table(L.caddy_fid_param_count, L.caddy_fid_param_info_get)
         if lib is not None:
             return table
         _fid_names = table
@@ -445,42 +441,18 @@ def find_fid_weights(cfg) -> Optional[Dict[str, torch.Tensor]]:
     return fid_inception_state(src)
 
 
-class InceptionFeatures:
+class InceptionFeatures(_EvalContext):
     """The FID feature network for frames of height x width: pytorch_fid's InceptionV3([3], resize_input=resize) on csrc/fid.hip.  Calling it on (bs, T, 3, H, W) or
     (n, 3, H, W) frames in [0, 1] returns an (n, 2048) float64 CPU tensor; more than `max_frames` frames run in chunks."""
 
     def __init__(self, height: int, width: int, max_frames: int, weights, resize: bool = True, lib=None, device=None):
-        from . import _lib
-        from .engine import CaddyError
-        self.lib = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
-        kind = getattr(self.lib, "_caddy_device_type", "cuda")
-        self.device = torch.device(device) if device is not None else torch.device(kind)
-        self.H, self.W, self.max_frames, self.resize = int(height), int(width), int(max_frames), bool(resize)
-        self._err = lambda: self.lib.caddy_last_error().decode()
+        super().__init__(height, width, max_frames, lib, device)
+        self.resize = bool(resize)
         table = fid_param_table(self.lib)
         state = fid_inception_state(weights, self.lib)
-        n = self.lib.caddy_fid_workspace_bytes(self.max_frames, self.H, self.W, int(self.resize))
-        if n == 0:
-            raise CaddyError(self._err())
-        raw = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-        self._ws = raw
-        self.ws_bytes = n
-        self.ctx = self.lib.caddy_fid_ctx_create(self.max_frames, self.H, self.W, int(self.resize), raw.data_ptr() + (-raw.data_ptr()) % 256, n)
-        if not self.ctx:
-            raise CaddyError(self._err())
-        flat = torch.zeros(self.lib.caddy_fid_param_floats(), dtype=torch.float32)
-        for name, off, shape in table:
-            t = state[name].detach().to(torch.float32)
-            if tuple(t.shape) != shape:
-                raise CaddyError(f"FID Inception {name}: shape {tuple(t.shape)}, expected {shape}")
-            flat[off:off + t.numel()] = t.reshape(-1)
-        flat = flat.to(self.device)
-        self._stream()
-        self._check(self.lib.caddy_load_fid_inception(self.ctx, flat.data_ptr()))
-
-    _check = FrameMetrics._check
-    _stream = FrameMetrics._stream
-    __del__ = FrameMetrics.__del__
+        self._create(self.lib.caddy_fid_workspace_bytes, self.lib.caddy_fid_ctx_create, int(self.resize))
+        # (22 M floats in ~470 tensors: assembled on the host and moved once)
+        self._load(self.lib.caddy_load_fid_inception, self.lib.caddy_fid_param_floats(), table, state, "FID Inception", staging="cpu")
 
     def set_precision(self, forward: int):
         """arithmetic of the convolutions: 16 (split f16, default) | 0 (exact fp32)"""
@@ -535,15 +507,10 @@ def _cached_fid(observations: torch.Tensor, weights, lib, resize: bool = True) -
     H, W = int(observations.shape[-2]), int(observations.shape[-1])
     n = int(np.prod(observations.shape[:-3]))
     lib = lib if lib is not None else _default_lib
-    key = (id(lib), str(observations.device), H, W, bool(resize), id(weights))
-    ctx = _fid_contexts.get(key)
-    if ctx is None:
-        area = 299 * 299 if resize else H * W
-        want = min(n, max(1, FID_FRAMES_256 * 299 * 299 // area))
-        ctx = InceptionFeatures(H, W, min(want, 1024), weights, resize, lib)
-        ctx._keep = weights      # (the cache key holds its id)
-        _fid_contexts[key] = ctx
-    return ctx
+    key = ("fid", id(lib), str(observations.device), H, W, bool(resize), id(weights))
+    area = 299 * 299 if resize else H * W
+    want = min(n, max(1, FID_FRAMES_256 * 299 * 299 // area))
+    return _cached(key, weights, lambda: InceptionFeatures(H, W, min(want, 1024), weights, resize, lib))
 
 
 def inception_features(observations: torch.Tensor, weights, lib=None, resize: bool = True) -> torch.Tensor:
