@@ -196,6 +196,38 @@ int caddy_debug_fid_fallback_layers(caddy_ctx* ctx);
  * and 8 x 8 stages (pytorch_fid/inception.py:83-123).  caddy_fid_macs_per_frame: multiply-accumulates of the 94 convolutions for one frame, counted from the graph. */
 int caddy_debug_fid_stage_ms(caddy_ctx* ctx, int on, float* ms5);
 double caddy_fid_macs_per_frame(int height, int width, int resize);
+/* --- FVD of the dataset evaluation (evaluation/metrics/fvd.py:67-126,188-226, used through IncrementalFVD by evaluation/dataset_evaluator.py:75,229,251 and the Breakout / BAIR
+ *     evaluators): the 400 logits RGB/inception_i3d/Mean:0 of the Kinetics-400 I3D per video, on the 3-D implicit-GEMM convolution, SAME-padded 3-D max pools and legacy bilinear
+ *     input stage of csrc/fvd.hip.  An FVD context is an evaluation context of its own kind: videos of `frames` frames of height x width in chunks of max_videos; resize != 0
+ *     mirrors fvd.py:49-56 (TF1 resize_bilinear to 224 x 224, align_corners=False, no half-pixel centres), resize == 0 runs the trunk at the frame's own size (the head's (2, 7, 7)
+ *     average window is then clipped to the final map and the logits averaged over what remains).  The mean / covariance / Frechet distance are host-side fp64 (metrics.py).
+ *     Bad geometry: 0 / NULL and caddy_last_error.  Destroy with caddy_ctx_destroy. --- */
+size_t caddy_fvd_workspace_bytes(int max_videos, int frames, int height, int width, int resize);                                     /* evaluation/metrics/fvd.py:49-56,188-190 */
+caddy_ctx* caddy_fvd_ctx_create(int max_videos, int frames, int height, int width, int resize, void* workspace, size_t bytes);       /* evaluation/metrics/fvd.py:67-71 */
+/* the network's tensors under the TF variable names of the module (evaluation/metrics/fvd.py:67-71; prefix RGB/inception_i3d/ and suffix :0 stripped), in graph order: per unit
+ * {unit}/conv_3d/w (DHWIO; info.shape = (KT KH KW, Cin, Cout), dhwio5 (nullable) receives the five sizes) and {unit}/batch_norm/beta, moving_mean, moving_variance;
+ * Logits/Conv3d_0c_1x1/conv_3d/w and /b; then (kind 4: optional, 1 when the module has none) the {unit}/batch_norm/gamma of the 57 units.  caddy_load_fvd_i3d takes a device
+ * buffer laid out by their offsets, folds every eval-mode batch norm (eps 1e-3) into its convolution and packs the weights for both arithmetics.  Not referenced after the call. */
+int caddy_fvd_param_count(void);                                                   /* evaluation/metrics/fvd.py:67-71 */
+int caddy_fvd_param_info_get(int index, caddy_param_info* out, int* dhwio5);       /* evaluation/metrics/fvd.py:67-71 */
+long caddy_fvd_param_floats(void);                                                 /* evaluation/metrics/fvd.py:67-71 */
+int caddy_load_fvd_i3d(caddy_ctx* ctx, const float* flat);                         /* evaluation/metrics/fvd.py:67-71 */
+/* arithmetic of the I3D convolutions: 16 = split f16 (default; the per-layer f16 range guard moves a layer that met |x| > 65504 to exact fp32) | 0 = exact fp32 MFMA.  The
+ * environment's CADDY_PRECISION=exact selects 0 at creation. */
+int caddy_set_fvd_precision(caddy_ctx* ctx, int forward);
+/* evaluation/metrics/fvd.py:106-126,207-226 (create_id3_embedding): videos = n x (frames, 3, height, width) planar fp32 in [0, 1] on the device; out_host (host memory) receives
+ * n x 400 doubles.  Bit-reproducible, and independent of max_videos: a video's logits depend on that video alone.  Waits for the stream. */
+int caddy_fvd_embeddings(caddy_ctx* ctx, const float* videos, int n, double* out_host);
+/* multiply-accumulates of the 57 convolutions + logits for one video, counted from the graph (evaluation/metrics/fvd.py:67-126) */
+double caddy_fvd_macs_per_video(int frames, int height, int width, int resize);
+/* tests: the outputs of Conv3d_2c_3x3, Mixed_3c, Mixed_4f, Mixed_5c (block 0..3; 192, 480, 832, 1024 channels) for the videos of the LAST chunk of the last caddy_fvd_embeddings,
+ * NCDHW fp32 into a device buffer (evaluation/metrics/fvd.py:118-125 runs the same graph); caddy_debug_fvd_fallback_layers: convolutions the range guard moved to exact fp32
+ * (-1: no FVD context) */
+int caddy_debug_fvd_block(caddy_ctx* ctx, int block, float* dst_ncdhw);
+int caddy_debug_fvd_fallback_layers(caddy_ctx* ctx);
+/* measurement: on != 0 records events at the stage boundaries of the following chunks; ms5 (nullable) receives the times of the last chunk's input stage (fvd.py:49-56), stem,
+ * Mixed_3, Mixed_4 and Mixed_5 + head */
+int caddy_debug_fvd_stage_ms(caddy_ctx* ctx, int on, float* ms5);
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per
@@ -371,6 +403,15 @@ int caddy_k_conv_igemm(const struct IgemmArgs* a, void* stream);
 int caddy_k_fid_pool(const struct TV* in, const struct TV* out, int mode, void* stream);      /* 0: MaxPool2d(3, 2); 1: avg_pool2d(3, 1, 1, count_include_pad=False); 2: max_pool2d(3, 1, 1) */
 int caddy_k_fid_global_avg(const struct TV* in, double* out, void* stream);
 int caddy_k_fid_stage(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, void* stream);
+/* kernels of the FVD feature network (csrc/fvd.h; reference: the conv3d / batch norm / max_pool3d ops of the I3D graph behind evaluation/metrics/fvd.py:67-71 and the
+ * tf.image.resize_bilinear of fvd.py:52) */
+struct Conv3dArgs; struct V5;
+size_t caddy_k_conv3d_weight_bytes(int Cin, int Cout, int KT, int KH, int KW);
+int caddy_k_conv3d_pack(const float* w_dhwio, const float* gamma, const float* beta, const float* mean, const float* var, float eps, const float* bias_in, int Cin, int Cout, int KT, int KH,
+                        int KW, void* w32, void* w16, float* bias_out, void* stream);
+int caddy_k_conv3d_igemm(const struct Conv3dArgs* a, void* stream);
+int caddy_k_fvd_pool(const struct V5* in, const struct V5* out, int kt, int kh, int kw, int st, int sh, int sw, void* stream);      /* max pool, TF SAME padding */
+int caddy_k_fvd_stage(const float* src, long frames, int Hs, int Ws, float* out, int Ho, int Wo, void* stream);
 int caddy_k_conv_took_direct(void);      /* 1: this thread's last caddy_k_conv_fwd ran on the latency kernel (ConvArgs.direct_ok; model/main_model/model.py:570-607 batch-1 roll-out layers) */
 /* BatchNorm fused with the convolutions around it (reference: the conv -> BatchNorm2d -> LeakyReLU chains of model/layers/residual_block.py:51-68,
  * same_block.py:34-47, up_block.py:31-45): per-tile partial sums from the producing conv's epilogue (ConvArgs.stats) -> finalisation without a pass over

@@ -5,6 +5,7 @@
 // (The model-less contexts of the dataset evaluation are eval_ctx.cpp's.)
 #include "net.h"
 #include "fid.h"
+#include "fvd.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1627,6 +1628,7 @@ void caddy_ctx_destroy(caddy_ctx* c) {
     if (c) for (ConvL* L : c->convs) if (L->off_ev) hipEventDestroy(L->off_ev);
     if (c && c->dstream) { hipStreamSynchronize(c->dstream); hipStreamDestroy(c->dstream); if (c->d_done) hipEventDestroy(c->d_done); }
     fid_free(c);
+    fvd_free(c);
     delete c;
 }
 int caddy_set_stream(caddy_ctx* c, void* s) { c->stream = (hipStream_t)s; return 0; }

@@ -7,7 +7,10 @@ keys are those of compute_positional_statistics: {m}/avg, {m}/var, {m}/{i}, {m}/
 `evaluation.lpips_vgg16_weights` + `evaluation.lpips_linear_weights`: metrics.find_lpips_weights) `lpips` is added (evaluation/metrics/lpips.py:14,33, on the
 HIP path: metrics.LPIPS); without them the keys are unchanged.  With Inception weights (`evaluation.fid_inception_weights`: metrics.find_fid_weights; `evaluation.fid_resize_input`,
 default true, is InceptionV3's resize_input) `fid` is added (evaluation/metrics/fid.py:140-159): the features of every frame of both datasets are collected inside the one batch
-loop (the reference makes two further passes over each loader), the statistics and the Frechet distance are host fp64.  FVD, IS and the plots are not computed.  The per-dataset evaluators that add the detection and action metrics of Breakout and BAIR are
+loop (the reference makes two further passes over each loader), the statistics and the Frechet distance are host fp64.  With I3D weights (`evaluation.fvd_i3d_weights`:
+metrics.find_fvd_weights; `evaluation.fvd_resize_input`, default true, is the 224 x 224 resize of evaluation/metrics/fvd.py:49-56) `fvd` is added (fvd.py:229-330): the I3D logits of
+the sequences are collected inside the same loop, and as IncrementalFVD feeds I3D 16 sequences at a time and drops the incomplete tail, only the first 16 floor(n / 16) sequences of
+each dataset enter the statistics (fewer than 16 raise).  IS and the plots are not computed.  The per-dataset evaluators that add the detection and action metrics of Breakout and BAIR are
 dataset_evaluator_breakout and dataset_evaluator_bair (ActionSpaceEvaluator below).
 """
 from typing import Dict
@@ -49,11 +52,18 @@ class DatasetEvaluator:
         self._fid_features = ([], [])
         if self.fid_state is None:
             self.logger.print("- fid skipped: no Inception weights configured (evaluation.fid_inception_weights)")
+        self.fvd_state = M.find_fvd_weights(config["evaluation"])
+        self.fvd_resize = bool(config["evaluation"].get("fvd_resize_input", True))
+        self._fvd_embeddings = ([], [])
+        if self.fvd_state is None:
+            self.logger.print("- fvd skipped: no I3D weights configured (evaluation.fvd_i3d_weights)")
         self.logger.print(self.NOT_COMPUTED)
         if self.lpips_state is not None:
             self.logger.print("- lpips is computed (LPIPS weights configured): the line above applies to it no longer")
         if self.fid_state is not None:
             self.logger.print("- fid is computed (Inception weights configured): the line above applies to it no longer")
+        if self.fvd_state is not None:
+            self.logger.print("- fvd is computed (I3D weights configured): the line above applies to it no longer")
 
     @staticmethod
     def check_range(values: Dict[str, torch.Tensor], which: str):
@@ -98,6 +108,22 @@ class DatasetEvaluator:
         self._fid_features = ([], [])
         return {"fid": float(M.fid_from_features(ref, gen))}
 
+    def collect_fvd_embeddings(self, reference_observations: torch.Tensor, generated_observations: torch.Tensor) -> None:
+        """I3D logits of this batch's sequences (evaluation/metrics/fvd.py:188-226); nothing without weights"""
+        if self.fvd_state is None:
+            return
+        self._fvd_embeddings[0].append(M.i3d_embeddings(reference_observations, self.fvd_state, resize=self.fvd_resize).numpy())
+        self._fvd_embeddings[1].append(M.i3d_embeddings(generated_observations, self.fvd_state, resize=self.fvd_resize).numpy())
+
+    def fvd_results(self) -> Dict:
+        """{"fvd": float} over the logits collected since the last call, complete batches of 16 sequences in loader order only (evaluation/metrics/fvd.py:270-280,322-324);
+        {} without weights"""
+        if self.fvd_state is None:
+            return {}
+        ref, gen = (np.concatenate(e, axis=0) for e in self._fvd_embeddings)
+        self._fvd_embeddings = ([], [])
+        return {"fvd": float(M.fvd_from_embeddings(ref[:M.fvd_batched_count(len(ref))], gen[:M.fvd_batched_count(len(gen))]))}
+
     def metric_names(self, names):
         return [m for m in names if m != "vgg_sim" or self.vgg_state is not None] + (["lpips"] if self.lpips_state is not None else [])
 
@@ -116,10 +142,12 @@ class DatasetEvaluator:
                 for m in names:
                     acc[m].append(values[m].numpy())
                 self.collect_fid_features(reference_observations, generated_observations)
+                self.collect_fvd_embeddings(reference_observations, generated_observations)
         results = {}
         for m in names:
             results.update(self.compute_positional_statistics(np.concatenate(acc[m], axis=0), m))
         results.update(self.fid_results())
+        results.update(self.fvd_results())
         return results
 
 
@@ -177,6 +205,7 @@ class ActionSpaceEvaluator(DatasetEvaluator):
                 for m in names:
                     acc[m].append(values[m].numpy())
                 self.collect_fid_features(reference_observations, generated_observations)
+                self.collect_fvd_embeddings(reference_observations, generated_observations)
                 found = self.detect(reference_observations, generated_observations)
                 for k, v in found.items():
                     detections.setdefault(k, []).append(v)
@@ -195,6 +224,7 @@ class ActionSpaceEvaluator(DatasetEvaluator):
             self.logger.print("- Warning: action accuracy results could not be computed")
         results.update(accuracy)
         results.update(self.fid_results())
+        results.update(self.fvd_results())
         return results
 
 

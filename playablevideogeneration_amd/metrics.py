@@ -16,7 +16,11 @@ The HIP-backed metrics run on a metrics context of libcaddy_hip.so (caddy_metric
                                                                                                           the Frechet distance in fp64 on the host
 LPIPS needs its weights from the caller (a torchvision vgg16 state dict plus the package's five `lin` tensors, see lpips_state), FID the pt_inception-2015-12-05 state dict
 (fid_inception_state): nothing is downloaded.
-(FVD -- I3D, 3-D convolutions --, the Inception Score and the Tennis detector stay out of scope.)"""
+    fvd                         evaluation/metrics/fvd.py:67-126,188-226 (Kinetics-400 I3D logits per video)  -- the I3D trunk on the 3-D implicit-GEMM convolution, SAME max
+                                                                                                          pools and legacy bilinear input stage of csrc/fvd.hip; the same host
+                                                                                                          fp64 statistics and Frechet distance as FID
+FVD needs the variables of the I3D module from the caller (fvd_i3d_state; INTEGRATION.md has the export recipe): nothing is downloaded.
+(The Inception Score and the Tennis detector stay out of scope.)"""
 import ctypes as C
 import re
 from typing import Dict, Optional
@@ -39,7 +43,7 @@ def psnr(reference_observations: torch.Tensor, generated_observations: torch.Ten
 SLOTS = ("mse", "motion_masked_mse", "psnr", "ssim", "vgg_sim", "ref_min", "ref_max", "gen_min", "gen_max")      # CADDY_FM_* of include/caddy_hip.h
 VGG_FRAMES_256 = 30      # frames per VGG19 chunk at 256 x 256 (scaled by the frame area): ~4 GB of feature maps
 _default_lib = None
-_contexts: Dict = {}      # every cached context: (kind, library, device, geometry, weights) -> FrameMetrics | LPIPS | InceptionFeatures
+_contexts: Dict = {}      # every cached context: (kind, library, device, geometry, weights) -> FrameMetrics | LPIPS | InceptionFeatures | I3DEmbeddings
 
 
 def set_library(lib) -> None:
@@ -82,6 +86,20 @@ def _bind(lib):
         lib.caddy_debug_fid_stage_ms.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.caddy_fid_macs_per_frame.restype = C.c_double
         lib.caddy_fid_macs_per_frame.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.caddy_fvd_workspace_bytes.restype = C.c_size_t
+        lib.caddy_fvd_workspace_bytes.argtypes = [C.c_int] * 5
+        lib.caddy_fvd_ctx_create.restype = C.c_void_p
+        lib.caddy_fvd_ctx_create.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_size_t]
+        lib.caddy_fvd_param_floats.restype = C.c_long
+        lib.caddy_fvd_param_info_get.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        lib.caddy_load_fvd_i3d.argtypes = [C.c_void_p, C.c_void_p]
+        lib.caddy_set_fvd_precision.argtypes = [C.c_void_p, C.c_int]
+        lib.caddy_fvd_embeddings.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        lib.caddy_debug_fvd_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.caddy_debug_fvd_fallback_layers.argtypes = [C.c_void_p]
+        lib.caddy_debug_fvd_stage_ms.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.caddy_fvd_macs_per_video.restype = C.c_double
+        lib.caddy_fvd_macs_per_video.argtypes = [C.c_int] * 4
         lib._caddy_metrics_bound = True
     return lib
 
@@ -558,6 +576,170 @@ def fid(reference_observations: torch.Tensor, generated_observations: torch.Tens
     """FID between two sets of frames in [0, 1] (evaluation/metrics/fid.py:140-159); every frame of every sequence is a sample"""
     return fid_from_features(inception_features(reference_observations, weights, lib, resize).numpy(),
                              inception_features(generated_observations, weights, lib, resize).numpy())
+
+
+# ---- FVD (caddy_fvd_embeddings + the host fp64 statistics of FID) ----
+FVD_DIM = 400
+FVD_SIZE = 224
+FVD_BATCH = 16                # IncrementalFVD feeds I3D 16 sequences at a time and drops the incomplete tail (evaluation/metrics/fvd.py:270-280,322-324)
+FVD_VIDEOS_30x224 = 8         # videos per I3D chunk at 30 frames of 224 x 224 (scaled by the video volume): ~1.7 GB of activations
+FVD_BLOCK_CHANNELS = (192, 480, 832, 1024)      # Conv3d_2c_3x3, Mixed_3c, Mixed_4f, Mixed_5c
+FVD_PREFIX = "RGB/inception_i3d/"
+FVD_ALIAS = {"Mixed_5b/Branch_2/Conv3d_0b_3x3/": "Mixed_5b/Branch_2/Conv3d_0a_3x3/"}      # the published checkpoint's name of that unit
+
+
+def fvd_param_table(lib=None):
+    """[(name, offset, shape, optional)] of caddy_fvd_param_info_get: the I3D variables under their TF names (prefix and `:0` stripped) in graph order, convolution filters
+    DHWIO; the trailing optional entries are the batch-norm gammas"""
+    from . import _lib
+    from .engine import ParamInfo
+    L = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
+    info, five, table = ParamInfo(), (C.c_int * 5)(), []
+    for i in range(L.caddy_fvd_param_count()):
+        L.caddy_fvd_param_info_get(i, C.byref(info), five)
+        shape = tuple(five) if five[0] else tuple(info.shape[:info.ndim])
+        table.append((info.name.decode(), int(info.offset), shape, info.kind == 4))
+    return table
+
+
+def _load_state_file(path):
+    if str(path).endswith(".npz"):
+        with np.load(path) as z:
+            return {k: torch.from_numpy(np.asarray(z[k])) for k in z.files}
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+def fvd_i3d_state(state, lib=None) -> Dict[str, torch.Tensor]:
+    """The I3D variables of the FVD module (evaluation/metrics/fvd.py:67-71) under the names of caddy_fvd_param_info_get, from a dict, an .npz or a torch.save'd dict.  Keys may
+    carry the `RGB/inception_i3d/` prefix (under any module scope), a `:0` suffix, a `module.` prefix or a {"state_dict": ...} wrapper; Mixed_5b/Branch_2's second convolution is accepted under either of
+    its two names; batch-norm statistics may have any shape that squeezes to (C,); gamma is optional (1 without it, as the module has no scale); other tensors are ignored.
+    A missing tensor raises CaddyError naming it, a wrong shape one naming the tensor."""
+    from .engine import CaddyError
+    src = _load_state_file(state) if isinstance(state, (str, bytes)) or hasattr(state, "__fspath__") else state
+    src = src.get("state_dict", src) if isinstance(src, dict) else src
+    clean = {}
+    for k, v in src.items():
+        k = k[:-2] if k.endswith(":0") else k
+        k = k[len("module."):] if k.startswith("module.") else k
+        k = k[k.index(FVD_PREFIX) + len(FVD_PREFIX):] if FVD_PREFIX in k else k      # (whatever scope the module was instantiated under)
+        clean[k] = v
+    out = {}
+    for name, _, shape, optional in fvd_param_table(lib):
+        keys = [name] + [name.replace(a, b) for a, b in FVD_ALIAS.items() if name.startswith(a)]
+        key = next((k for k in keys if k in clean), None)
+        if key is None:
+            if optional:
+                continue
+            raise CaddyError(f"FVD I3D weights lack {name}")
+        t = torch.as_tensor(clean[key])
+        if len(shape) == 1 and t.numel() == shape[0]:
+            t = t.reshape(shape)
+        if tuple(t.shape) != shape:
+            raise CaddyError(f"FVD I3D {name}: shape {tuple(t.shape)}, expected {shape}")
+        out[name] = t
+    return out
+
+
+def find_fvd_weights(cfg) -> Optional[Dict[str, torch.Tensor]]:
+    """config["evaluation"] -> fvd_i3d_state(...) of `fvd_i3d_weights` (a path or a dict); None when it is not configured.  Nothing is downloaded."""
+    src = cfg.get("fvd_i3d_weights", None)
+    return None if src is None else fvd_i3d_state(src)
+
+
+class I3DEmbeddings(_EvalContext):
+    """The FVD feature network for videos of `frames` frames of height x width: the Kinetics-400 I3D of evaluation/metrics/fvd.py:67-126 on csrc/fvd.hip.  Calling it on
+    (bs, frames, 3, H, W) videos in [0, 1] returns a (bs, 400) float64 CPU tensor; more than `max_videos` videos run in chunks."""
+
+    def __init__(self, frames: int, height: int, width: int, max_videos: int, weights, resize: bool = True, lib=None, device=None):
+        super().__init__(height, width, max_videos, lib, device)
+        self.T, self.resize, self.max_videos = int(frames), bool(resize), int(max_videos)
+        state = fvd_i3d_state(weights, self.lib)
+        table = fvd_param_table(self.lib)
+        for name, _, shape, optional in table:
+            if optional and name not in state:
+                state[name] = torch.ones(shape)
+        flat_table = [(name, off, shape) for name, off, shape, _ in table]
+        self._create(lambda m, h, w, r: self.lib.caddy_fvd_workspace_bytes(m, self.T, h, w, r),
+                     lambda m, h, w, r, ws, n: self.lib.caddy_fvd_ctx_create(m, self.T, h, w, r, ws, n), int(self.resize))
+        self._load(self.lib.caddy_load_fvd_i3d, self.lib.caddy_fvd_param_floats(), flat_table, state, "FVD I3D", staging="cpu")
+
+    def set_precision(self, forward: int):
+        """arithmetic of the convolutions: 16 (split f16, default) | 0 (exact fp32)"""
+        self._check(self.lib.caddy_set_fvd_precision(self.ctx, int(forward)))
+
+    def fallback_layers(self) -> int:
+        return int(self.lib.caddy_debug_fvd_fallback_layers(self.ctx))
+
+    def __call__(self, observations: torch.Tensor) -> torch.Tensor:
+        o = observations
+        if o.dim() != 5 or o.shape[2] != 3 or int(o.shape[1]) != self.T or tuple(o.shape[3:]) != (self.H, self.W):
+            raise ValueError(f"expected (bs, {self.T}, 3, {self.H}, {self.W}) videos, got {tuple(o.shape)}")
+        n = int(o.shape[0])
+        o = o.detach().to(self.device, torch.float32).contiguous()
+        out = torch.empty(n, FVD_DIM, dtype=torch.float64)
+        self._stream()
+        self._check(self.lib.caddy_fvd_embeddings(self.ctx, o.data_ptr(), n, out.data_ptr()))
+        self.last_videos = (n - 1) % self.max_videos + 1
+        return out
+
+    def block(self, index: int) -> torch.Tensor:
+        """output of Conv3d_2c_3x3 / Mixed_3c / Mixed_4f / Mixed_5c (index 0..3) for the videos of the last chunk of the last call, (videos, C, t, h, w) float32 on the CPU"""
+        t, h, w = _fvd_block_sizes(self.T, self.H, self.W, self.resize)[index]
+        buf = torch.empty(self.last_videos, FVD_BLOCK_CHANNELS[index], t, h, w, dtype=torch.float32, device=self.device)
+        self._check(self.lib.caddy_debug_fvd_block(self.ctx, int(index), buf.data_ptr()))
+        return buf.cpu()
+
+    def stage_times(self, on: bool = True, read: bool = False):
+        """per-stage milliseconds of the last timed chunk (input stage, stem, Mixed_3, Mixed_4, Mixed_5 + head) when `read`; `on` switches the event recording"""
+        ms = (C.c_float * 5)()
+        self._check(self.lib.caddy_debug_fvd_stage_ms(self.ctx, int(on), ms if read else None))
+        return list(ms) if read else None
+
+
+def _fvd_block_sizes(T: int, H: int, W: int, resize: bool):
+    """(t, h, w) of the four tapped outputs: SAME padding, so every stride-2 layer maps s to ceil(s / 2)"""
+    def halve(s, times):
+        for _ in range(times):
+            s = (s + 1) // 2
+        return s
+    h, w = (FVD_SIZE, FVD_SIZE) if resize else (int(H), int(W))
+    return [(halve(T, 1), halve(h, 2), halve(w, 2)), (halve(T, 1), halve(h, 3), halve(w, 3)), (halve(T, 2), halve(h, 4), halve(w, 4)), (halve(T, 3), halve(h, 5), halve(w, 5))]
+
+
+def _cached_fvd(observations: torch.Tensor, weights, lib, resize: bool = True) -> I3DEmbeddings:
+    """the FVD context of this library, device, video geometry and weights (cached like _cached_fid)"""
+    n, T, _, H, W = (int(v) for v in observations.shape)
+    lib = lib if lib is not None else _default_lib
+    key = ("fvd", id(lib), str(observations.device), T, H, W, bool(resize), id(weights))
+    volume = T * (FVD_SIZE * FVD_SIZE if resize else H * W)
+    want = min(n, max(1, FVD_VIDEOS_30x224 * 30 * FVD_SIZE * FVD_SIZE // volume))
+    return _cached(key, weights, lambda: I3DEmbeddings(T, H, W, min(want, 1024), weights, resize, lib))
+
+
+def i3d_embeddings(observations: torch.Tensor, weights, lib=None, resize: bool = True) -> torch.Tensor:
+    """(bs, T, 3, H, W) videos in [0, 1] -> (bs, 400) float64 I3D logits (evaluation/metrics/fvd.py:188-226)"""
+    if weights is None:
+        raise ValueError("FVD needs I3D weights (see fvd_i3d_state)")
+    return _cached_fvd(observations, weights, lib, resize)(observations)
+
+
+def fvd_from_embeddings(reference_embeddings, generated_embeddings) -> float:
+    """Frechet distance of two sets of I3D logits (evaluation/metrics/fvd.py:129-152 calls tfgan's frechet_classifier_distance_from_activations): activation_statistics +
+    frechet_distance.  tfgan's function is the same quantity -- fp64, unbiased covariance, Tr sqrt(S1 S2); the equality is mathematical, it is not tested against tfgan."""
+    return fid_from_features(reference_embeddings, generated_embeddings)
+
+
+def fvd_batched_count(n: int) -> int:
+    """sequences of a dataset of n that enter the statistics: IncrementalFVD's complete batches of 16 (evaluation/metrics/fvd.py:270-280,322-324); fewer than 16 raise, as there"""
+    if n < FVD_BATCH:
+        raise Exception(f"FVD needs at least {FVD_BATCH} sequences per dataset (it feeds I3D {FVD_BATCH} at a time and drops the incomplete tail), got {n}")
+    return FVD_BATCH * (n // FVD_BATCH)
+
+
+def fvd(reference_videos: torch.Tensor, generated_videos: torch.Tensor, weights, lib=None, resize: bool = True) -> float:
+    """FVD between two sets of (n, T, 3, H, W) videos in [0, 1] (evaluation/metrics/fvd.py:229-330): the first 16 floor(n / 16) videos of each set, in order"""
+    r, g = reference_videos[:fvd_batched_count(len(reference_videos))], generated_videos[:fvd_batched_count(len(generated_videos))]
+    return fvd_from_embeddings(i3d_embeddings(r, weights, lib, resize).numpy(), i3d_embeddings(g, weights, lib, resize).numpy())
 
 
 def rollout_quality(model, batch_tuple, ground_truth_observations_init: int = 1, gumbel_temperature: float = 1.0) -> dict:
