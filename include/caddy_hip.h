@@ -196,6 +196,32 @@ int caddy_debug_fid_fallback_layers(caddy_ctx* ctx);
  * and 8 x 8 stages (pytorch_fid/inception.py:83-123).  caddy_fid_macs_per_frame: multiply-accumulates of the 94 convolutions for one frame, counted from the graph. */
 int caddy_debug_fid_stage_ms(caddy_ctx* ctx, int on, float* ms5);
 double caddy_fid_macs_per_frame(int height, int width, int resize);
+/* --- Inception Score of the dataset evaluation (evaluation/metrics/inception_score.py:17-65; its call is commented out in evaluation/dataset_evaluator.py:74, so the evaluators
+ *     compute it only when weights are configured): per frame the softmax over the 1000 logits of torchvision's inception_v3(transform_input=False).eval() behind a bilinear
+ *     299 x 299 resize (inception_score.py:20-22,41-43).  The network is the FID trunk's graph in its torchvision flavour -- no 2 x - 1 on the input, F.avg_pool2d(3, 1, 1) with
+ *     count_include_pad=True in the A / C / E blocks (both E blocks average), then the global average, fc = Linear(2048, 1000) as a 1 x 1 implicit-GEMM convolution and the
+ *     wave-per-frame softmax of csrc/fid.hip.  An IS context is an evaluation context of its own kind; resize == 0 runs the network at the frame's own size (>= 75 x 75; tests).
+ *     The score itself is host-side fp64 (metrics.py).  Destroy with caddy_ctx_destroy. --- */
+size_t caddy_is_workspace_bytes(int max_frames, int height, int width, int resize);                                     /* evaluation/metrics/inception_score.py:20-22 */
+caddy_ctx* caddy_is_ctx_create(int max_frames, int height, int width, int resize, void* workspace, size_t bytes);       /* evaluation/metrics/inception_score.py:20-22 */
+/* torchvision's names (inception_score.py:20): the 94 BasicConv2d of the trunk as for caddy_fid_param_info_get, then fc.weight (1000, 2048) and fc.bias; AuxLogits.* does not run
+ * in eval mode and has no entry.  caddy_load_is_inception takes a device buffer laid out by the offsets; it is not referenced after the call. */
+int caddy_is_param_count(void);                                       /* evaluation/metrics/inception_score.py:20 */
+int caddy_is_param_info_get(int index, caddy_param_info* out);        /* evaluation/metrics/inception_score.py:20 */
+long caddy_is_param_floats(void);                                     /* evaluation/metrics/inception_score.py:20 */
+int caddy_load_is_inception(caddy_ctx* ctx, const float* flat);       /* evaluation/metrics/inception_score.py:20-21 */
+/* arithmetic of the convolutions and of fc: 16 = split f16 (default, with the per-layer f16 range guard) | 0 = exact fp32 MFMA; CADDY_PRECISION=exact selects 0 at creation */
+int caddy_set_is_precision(caddy_ctx* ctx, int forward);              /* evaluation/metrics/inception_score.py:42 */
+/* inception_score.py:39-44: frames = n x (3, height, width) planar fp32 in [0, 1] on the device; out_host (host memory) receives n x 1000 fp32 probabilities.  Bit-reproducible and
+ * independent of max_frames.  Waits for the stream. */
+int caddy_is_probabilities(caddy_ctx* ctx, const float* frames, int n, float* out_host);      /* evaluation/metrics/inception_score.py:39-44 */
+/* tests and measurement: the logits (frames x 1000 fp32, into a device buffer) of the LAST chunk of the last caddy_is_probabilities; the layers the range guard moved to exact fp32
+ * (-1: no IS context); event times of the last chunk's input stage, stem, 35 x 35, 17 x 17, 8 x 8 stages and head (fc + softmax) as caddy_debug_fid_stage_ms; multiply-accumulates
+ * of one frame (94 convolutions + fc) */
+int caddy_debug_is_logits(caddy_ctx* ctx, float* dst);                /* evaluation/metrics/inception_score.py:42 */
+int caddy_debug_is_fallback_layers(caddy_ctx* ctx);                   /* evaluation/metrics/inception_score.py:42 */
+int caddy_debug_is_stage_ms(caddy_ctx* ctx, int on, float* ms6);      /* evaluation/metrics/inception_score.py:41-43 */
+double caddy_is_macs_per_frame(int height, int width, int resize);    /* evaluation/metrics/inception_score.py:41-42 */
 /* --- FVD of the dataset evaluation (evaluation/metrics/fvd.py:67-126,188-226, used through IncrementalFVD by evaluation/dataset_evaluator.py:75,229,251 and the Breakout / BAIR
  *     evaluators): the 400 logits RGB/inception_i3d/Mean:0 of the Kinetics-400 I3D per video, on the 3-D implicit-GEMM convolution, SAME-padded 3-D max pools and legacy bilinear
  *     input stage of csrc/fvd.hip.  An FVD context is an evaluation context of its own kind: videos of `frames` frames of height x width in chunks of max_videos; resize != 0
@@ -400,9 +426,13 @@ size_t caddy_k_igemm_weight_bytes(int Cin, int Cout, int KH, int KW);
 int caddy_k_igemm_pack(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps, const float* bias_in, int Cin, int Cout, int KH, int KW,
                        void* w32, void* w16, float* bias_out, void* stream);
 int caddy_k_conv_igemm(const struct IgemmArgs* a, void* stream);
-int caddy_k_fid_pool(const struct TV* in, const struct TV* out, int mode, void* stream);      /* 0: MaxPool2d(3, 2); 1: avg_pool2d(3, 1, 1, count_include_pad=False); 2: max_pool2d(3, 1, 1) */
+int caddy_k_fid_pool(const struct TV* in, const struct TV* out, int mode, void* stream);      /* 0: MaxPool2d(3, 2); 1: avg_pool2d(3, 1, 1, count_include_pad=False); 2: max_pool2d(3, 1, 1); 3: avg_pool2d(3, 1, 1) */
 int caddy_k_fid_global_avg(const struct TV* in, double* out, void* stream);
 int caddy_k_fid_stage(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, void* stream);
+/* the Inception Score's variants (evaluation/metrics/inception_score.py:22,41-43): caddy_k_fid_pool's mode 3 is torchvision's F.avg_pool2d(x, 3, 1, 1) (count_include_pad=True);
+ * caddy_k_is_stage is caddy_k_fid_stage without the 2 x - 1; caddy_k_is_softmax: softmax over the C columns of n rows of pitch ld_in -> ld_out floats, one wave64 per row */
+int caddy_k_is_stage(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, void* stream);                      /* evaluation/metrics/inception_score.py:22,41 */
+int caddy_k_is_softmax(const float* logits, float* probs, int n, int C, long ld_in, long ld_out, void* stream);               /* evaluation/metrics/inception_score.py:43 */
 /* kernels of the FVD feature network (csrc/fvd.h; reference: the conv3d / batch norm / max_pool3d ops of the I3D graph behind evaluation/metrics/fvd.py:67-71 and the
  * tf.image.resize_bilinear of fvd.py:52) */
 struct Conv3dArgs; struct V5;

@@ -1,4 +1,4 @@
-// Evaluation contexts (eval_ctx.h): the shared scaffold, and the frame-metric, LPIPS and platform-position entry points built on it.  The FID kind and its entry points live
+// Evaluation contexts (eval_ctx.h): the shared scaffold, and the frame-metric, LPIPS and platform-position entry points built on it.  The FID and Inception Score kinds and their entry points live
 // with their graph in fid.hip.  Nothing here allocates device memory: a context lives in the caller's workspace.
 #include "eval_ctx.h"
 #include "frame_metrics.h"
@@ -18,7 +18,7 @@ bool ctx_needs(caddy_ctx* c, int kinds, const char* who) {
         return false;
     }
     if (c && (c->kind & kinds)) return true;
-    set_error(std::string(who) + " needs a context from " + (kinds & CTX_METRICS ? "caddy_metrics_ctx_create" : kinds & CTX_LPIPS ? "caddy_lpips_ctx_create" : kinds & CTX_FID ? "caddy_fid_ctx_create" : "caddy_fvd_ctx_create"));
+    set_error(std::string(who) + " needs a context from " + (kinds & CTX_METRICS ? "caddy_metrics_ctx_create" : kinds & CTX_LPIPS ? "caddy_lpips_ctx_create" : kinds & CTX_FID ? "caddy_fid_ctx_create" : kinds & CTX_IS ? "caddy_is_ctx_create" : "caddy_fvd_ctx_create"));
     return false;
 }
 

@@ -31,12 +31,16 @@ int igemm_pack(const float* w, const float* gamma, const float* beta, const floa
                void* w32, void* w16, float* bias_out, hipStream_t st);
 int igemm_launch(const IgemmArgs& a, hipStream_t st);
 
-// 3 x 3 poolings on NHWC views (C a multiple of 4).  mode 0: MaxPool2d(3, 2) unpadded; 1: avg_pool2d(3, 1, 1, count_include_pad=False); 2: max_pool2d(3, 1, 1)
+// 3 x 3 poolings on NHWC views (C a multiple of 4).  mode 0: MaxPool2d(3, 2) unpadded; 1: avg_pool2d(3, 1, 1, count_include_pad=False); 2: max_pool2d(3, 1, 1);
+// 3: avg_pool2d(3, 1, 1) with torch's default count_include_pad=True (the sum over the window inside the map, divided by 9 everywhere)
 int fid_pool_launch(const TV& in, const TV& out, int mode, hipStream_t st);
 // mean over H x W of every channel, fp32 values summed in fp64 in pixel order: out[n * C + c]
 int fid_global_avg_launch(const TV& in, double* out, hipStream_t st);
-// (n, 3, Hs, Ws) planar fp32 in [0, 1] -> NHWC pitch-4 image of Ho x Wo: F.interpolate(mode='bilinear', align_corners=False) when the sizes differ, then 2 x - 1
-int fid_stage_launch(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, hipStream_t st);
+// (n, 3, Hs, Ws) planar fp32 in [0, 1] -> NHWC pitch-4 image of Ho x Wo: F.interpolate(mode='bilinear', align_corners=False) when the sizes differ, then 2 x - 1 (normalise) or
+// the value as it is (the Inception Score's network: evaluation/metrics/inception_score.py:20-22,41)
+int fid_stage_launch(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, hipStream_t st, int normalise = 1);
+// softmax over the C columns of each of n rows (pitches ld_in / ld_out floats), fp32, one wave64 per row: evaluation/metrics/inception_score.py:43
+int is_softmax_launch(const float* logits, float* probs, int n, int C, long ld_in, long ld_out, hipStream_t st);
 
 struct caddy_ctx;
 void fid_free(caddy_ctx* c);      // releases caddy_ctx::fid (caddy_ctx_destroy)

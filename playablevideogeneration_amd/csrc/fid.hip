@@ -171,9 +171,10 @@ template <int MODE>
 __global__ __launch_bounds__(256) void k_fid_pool(TV in, TV out, long total) {
     const int C4 = out.C >> 2;
     const int stride = MODE == 0 ? 2 : 1, pad = MODE == 0 ? 0 : 1;
+    constexpr bool AVG = MODE == 1 || MODE == 3;      // 3: count_include_pad=True, the padding adds zeros and the divisor is 9 everywhere
     for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int c = (int)(i % C4); long q = i / C4; const int x = (int)(q % out.W); q /= out.W; const int y = (int)(q % out.H); const long n = q / out.H;
-        float4 m = MODE == 1 ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        float4 m = AVG ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
         int cnt = 0;
         for (int dy = 0; dy < 3; dy++) {
             const int iy = y * stride - pad + dy;
@@ -182,11 +183,12 @@ __global__ __launch_bounds__(256) void k_fid_pool(TV in, TV out, long total) {
                 const int ix = x * stride - pad + dx;
                 if (ix < 0 || ix >= in.W) continue;
                 const float4 v = *reinterpret_cast<const float4*>(in.p + n * in.sn + ((long)iy * in.W + ix) * in.ld + 4 * c);
-                if (MODE == 1) { m.x += v.x; m.y += v.y; m.z += v.z; m.w += v.w; cnt++; }
+                if (AVG) { m.x += v.x; m.y += v.y; m.z += v.z; m.w += v.w; cnt++; }
                 else { m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w); }
             }
         }
         if (MODE == 1) { const float d = (float)cnt; m.x /= d; m.y /= d; m.z /= d; m.w /= d; }
+        if (MODE == 3) { m.x /= 9.f; m.y /= 9.f; m.z /= 9.f; m.w /= 9.f; }
         *reinterpret_cast<float4*>(out.p + n * out.sn + ((long)y * out.W + x) * out.ld + 4 * c) = m;
     }
 }
@@ -214,6 +216,7 @@ __device__ __forceinline__ void lerp_coord(int d, float scale, int in, int& i0, 
     i1 = i0 < in - 1 ? i0 + 1 : i0;
     l1 = s - (float)i0; l0 = 1.f - l1;
 }
+template <bool NORM>      // NORM: pytorch_fid's 2 x - 1; without it the frames enter the first convolution as they are (torchvision's transform_input=False)
 __global__ __launch_bounds__(256) void k_fid_stage(const float* src, float* out, long npix, int Hs, int Ws, int Ho, int Wo, float sy, float sx) {
     const long hws = (long)Hs * Ws;
     const bool same = Hs == Ho && Ws == Wo;
@@ -231,8 +234,26 @@ __global__ __launch_bounds__(256) void k_fid_stage(const float* src, float* out,
                 v[c] = ly0 * (lx0 * p[(long)y0 * Ws + x0] + lx1 * p[(long)y0 * Ws + x1]) + ly1 * (lx0 * p[(long)y1 * Ws + x0] + lx1 * p[(long)y1 * Ws + x1]);
             }
         }
-        reinterpret_cast<float4*>(out)[q] = make_float4(2.f * v[0] - 1.f, 2.f * v[1] - 1.f, 2.f * v[2] - 1.f, 0.f);
+        reinterpret_cast<float4*>(out)[q] = NORM ? make_float4(2.f * v[0] - 1.f, 2.f * v[1] - 1.f, 2.f * v[2] - 1.f, 0.f) : make_float4(v[0], v[1], v[2], 0.f);
     }
+}
+
+// F.softmax over the C logits of a frame (evaluation/metrics/inception_score.py:43).  One wave64 per frame, four frames per workgroup; lane l holds columns l, l + 64, ...
+// Max, then sum of exp(z - max), each by an xor-butterfly over the 64 lanes: every lane ends with the same bits, the order of the additions is fixed by the lane
+// number alone, so a frame's probabilities depend on nothing but its logits.  No LDS, no atomics; ~10 VGPRs, so occupancy is bounded by the grid, not by registers.
+__global__ __launch_bounds__(256) void k_is_softmax(const float* logits, float* probs, int n, int C, long ld_in, long ld_out) {
+    const int lane = threadIdx.x & 63;
+    const long f = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (f >= n) return;      // (wave-uniform: the whole wave leaves)
+    const float* z = logits + f * ld_in;
+    float mx = -INFINITY;
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, z[c]);
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += expf(z[c] - mx);
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    float* p = probs + f * ld_out;
+    for (int c = lane; c < C; c += 64) p[c] = expf(z[c] - mx) / s;
 }
 
 inline unsigned grid_for(long items) { long b = (items + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
@@ -271,7 +292,7 @@ int igemm_launch(const IgemmArgs& a, hipStream_t st) {
 }
 
 int fid_pool_launch(const TV& in, const TV& out, int mode, hipStream_t st) {
-    if (mode < 0 || mode > 2 || in.C != out.C || (in.C % 4) || (in.ld % 4) || (out.ld % 4) || in.N != out.N) return -1;
+    if (mode < 0 || mode > 3 || in.C != out.C || (in.C % 4) || (in.ld % 4) || (out.ld % 4) || in.N != out.N) return -1;
     const int Ho = mode == 0 ? (in.H - 3) / 2 + 1 : in.H, Wo = mode == 0 ? (in.W - 3) / 2 + 1 : in.W;
     if (in.H < 3 && mode == 0) return -1;
     if (out.H != Ho || out.W != Wo) return -1;
@@ -279,7 +300,8 @@ int fid_pool_launch(const TV& in, const TV& out, int mode, hipStream_t st) {
     const dim3 g(grid_for(total)), b(256);
     if (mode == 0) hipLaunchKernelGGL((k_fid_pool<0>), g, b, 0, st, in, out, total);
     else if (mode == 1) hipLaunchKernelGGL((k_fid_pool<1>), g, b, 0, st, in, out, total);
-    else hipLaunchKernelGGL((k_fid_pool<2>), g, b, 0, st, in, out, total);
+    else if (mode == 2) hipLaunchKernelGGL((k_fid_pool<2>), g, b, 0, st, in, out, total);
+    else hipLaunchKernelGGL((k_fid_pool<3>), g, b, 0, st, in, out, total);
     return launch_ok();
 }
 
@@ -290,10 +312,19 @@ int fid_global_avg_launch(const TV& in, double* out, hipStream_t st) {
     return launch_ok();
 }
 
-int fid_stage_launch(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, hipStream_t st) {
+int fid_stage_launch(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, hipStream_t st, int normalise) {
     if (!src || !out || n < 1 || Hs < 1 || Ws < 1 || Ho < 1 || Wo < 1) return -1;
     const long npix = (long)n * Ho * Wo;
-    hipLaunchKernelGGL(k_fid_stage, dim3(grid_for(npix)), dim3(256), 0, st, src, out, npix, Hs, Ws, Ho, Wo, (float)Hs / (float)Ho, (float)Ws / (float)Wo);
+    const dim3 g(grid_for(npix)), b(256);
+    const float sy = (float)Hs / (float)Ho, sx = (float)Ws / (float)Wo;
+    if (normalise) hipLaunchKernelGGL((k_fid_stage<true>), g, b, 0, st, src, out, npix, Hs, Ws, Ho, Wo, sy, sx);
+    else hipLaunchKernelGGL((k_fid_stage<false>), g, b, 0, st, src, out, npix, Hs, Ws, Ho, Wo, sy, sx);
+    return launch_ok();
+}
+
+int is_softmax_launch(const float* logits, float* probs, int n, int C, long ld_in, long ld_out, hipStream_t st) {
+    if (!logits || !probs || n < 1 || C < 1 || ld_in < C || ld_out < C) return -1;
+    hipLaunchKernelGGL(k_is_softmax, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, logits, probs, n, C, ld_in, ld_out);
     return launch_ok();
 }
 
@@ -303,17 +334,22 @@ int fid_stage_launch(const float* src, int n, int Hs, int Ws, float* out, int Ho
 // ---------------------------------------------------------------------------------------------------------------------
 #define FID_EPS 0.001f
 #define FID_DIM 2048
-struct FidSpec { char name[96]; int cin, cout, kh, kw, stride, ph, pw; };
+#define IS_CLASSES 1000
+enum { FLAVOUR_FID = 0,      // pytorch_fid's patched network to pool_3
+       FLAVOUR_TV = 1 };     // torchvision's inception_v3(transform_input=False).eval() to the softmax (evaluation/metrics/inception_score.py:20-22,41-43)
+struct FidSpec { char name[96]; int cin, cout, kh, kw, stride, ph, pw; int linear; };      // linear: nn.Linear as a 1 x 1 convolution (weight + bias, no BatchNorm, no ReLU)
 struct FidLayer { FidSpec s; void* w32 = nullptr; void* w16 = nullptr; float* bias = nullptr; long off = 0; };
 struct FidState {
     int resize = 1, Hn = 299, Wn = 299;      // size the trunk runs at
+    int flavour = FLAVOUR_FID;
     std::vector<FidLayer> L;
     bool loaded = false;
     int precision = PREC_F16X3;
     double* feat = nullptr;                  // max_frames x 2048
+    float *feat32 = nullptr, *logits = nullptr, *probs = nullptr;      // FLAVOUR_TV: the narrowed features (fc's input), max_frames x 1000 logits and probabilities
     TV taps[3]{};                            // block outputs 0 .. 2 of the last chunk (InceptionV3.BLOCK_INDEX_BY_DIM: 64, 192, 768 channels)
     int last_nf = 0;
-    hipEvent_t ev[6] = {};
+    hipEvent_t ev[7] = {};
     bool timed = false, timed_ran = false;
 };
 
@@ -327,16 +363,17 @@ struct FidWalk {
     caddy_ctx* c = nullptr; FidState* F = nullptr;
     std::vector<FidSpec>* spec = nullptr;
     int li = 0;
+    int flavour = FLAVOUR_FID;
     double macs = 0.0;
     FMap make(float* p, int N, int H, int W, int C) { return FMap{p, N, H, W, C, (long)H * W * C, C}; }
     FMap temp(int N, int H, int W, int C) { return make(spec ? nullptr : (float*)c->act.alloc((size_t)N * H * W * C * 4), N, H, W, C); }
-    FMap conv(const std::string& name, const FMap& x, int cout, int kh, int kw, int stride, int ph, int pw, const FMap* into = nullptr) {
+    FMap conv(const std::string& name, const FMap& x, int cout, int kh, int kw, int stride, int ph, int pw, const FMap* into = nullptr, int linear = 0) {
         const int Ho = igemm_out(x.H, kh, stride, ph), Wo = igemm_out(x.W, kw, stride, pw);
         FMap out = into ? *into : temp(x.N, Ho, Wo, cout);
         macs += (double)x.N * Ho * Wo * cout * kh * kw * x.C;
         if (spec) {
             FidSpec s{}; snprintf(s.name, sizeof(s.name), "%s", name.c_str());
-            s.cin = x.C; s.cout = cout; s.kh = kh; s.kw = kw; s.stride = stride; s.ph = ph; s.pw = pw;
+            s.cin = x.C; s.cout = cout; s.kh = kh; s.kw = kw; s.stride = stride; s.ph = ph; s.pw = pw; s.linear = linear;
             spec->push_back(s);
             return out;
         }
@@ -350,7 +387,7 @@ struct FidWalk {
         a.precision = (F->precision == PREC_FP32 || c->layer_fallback[i]) ? PREC_FP32 : PREC_F16X3;      // a layer whose input left the f16 range runs exact from then on
         a.w = a.precision == PREC_FP32 ? L.w32 : L.w16;
         a.nchunk = igemm_nchunk(x.C, kh, kw); a.gather = igemm_gather(x.C, kh, kw);
-        a.Cout = cout; a.bias = L.bias; a.relu = 1;
+        a.Cout = cout; a.bias = L.bias; a.relu = linear ? 0 : 1;
         a.out = out.p; a.out_sn = out.sn; a.out_ld = out.ld;
         a.sat_flag = c->sat_flag + i;
         c->ck(igemm_launch(a, c->stream), L.s.name);
@@ -362,6 +399,8 @@ struct FidWalk {
         if (!spec && !c->dry) c->ck(fid_pool_launch(tv(x), tv(out), mode, c->stream), "fid pool");
         return out;
     }
+    // the A / C / E_1 average: padding-excluding under the FID patches, torchvision's own F.avg_pool2d(x, 3, 1, 1) (count_include_pad=True) otherwise
+    int avg_mode() const { return flavour == FLAVOUR_TV ? 3 : 1; }
     // inception.py:205-227
     void blockA(const std::string& n, const FMap& x, int pf, const FMap& out) {
         FMap s;
@@ -371,7 +410,7 @@ struct FidWalk {
         t = conv(n + ".branch3x3dbl_1", x, 64, 1, 1, 1, 0, 0);
         t = conv(n + ".branch3x3dbl_2", t, 96, 3, 3, 1, 1, 1);
         s = cslice(out, 128, 96); conv(n + ".branch3x3dbl_3", t, 96, 3, 3, 1, 1, 1, &s);
-        t = pool(x, 1);
+        t = pool(x, avg_mode());
         s = cslice(out, 224, pf); conv(n + ".branch_pool", t, pf, 1, 1, 1, 0, 0, &s);
     }
     // torchvision InceptionB (not patched)
@@ -395,7 +434,7 @@ struct FidWalk {
         t = conv(n + ".branch7x7dbl_3", t, c7, 1, 7, 1, 0, 3);
         t = conv(n + ".branch7x7dbl_4", t, c7, 7, 1, 1, 3, 0);
         s = cslice(out, 384, 192); conv(n + ".branch7x7dbl_5", t, 192, 1, 7, 1, 0, 3, &s);
-        t = pool(x, 1);
+        t = pool(x, avg_mode());
         s = cslice(out, 576, 192); conv(n + ".branch_pool", t, 192, 1, 1, 1, 0, 0, &s);
     }
     // torchvision InceptionD (not patched)
@@ -409,7 +448,7 @@ struct FidWalk {
         s = cslice(out, 320, 192); conv(n + ".branch7x7x3_4", t, 192, 3, 3, 2, 0, 0, &s);
         s = cslice(out, 512, x.C); pool(x, 0, &s);
     }
-    // inception.py:258-322 (pool_mode 1: E_1's padding-excluding average, 2: E_2's max pool)
+    // inception.py:258-322 (pool_mode 1: E_1's padding-excluding average, 2: E_2's max pool; torchvision's own E blocks both take mode 3)
     void blockE(const std::string& n, const FMap& x, int pool_mode, const FMap& out) {
         FMap s;
         s = cslice(out, 0, 320); conv(n + ".branch1x1", x, 320, 1, 1, 1, 0, 0, &s);
@@ -432,7 +471,7 @@ struct FidWalk {
         mark(0);
         FMap img = make(spec ? nullptr : (float*)A->alloc((size_t)N * Hn * Wn * 16), N, Hn, Wn, 3);
         img.ld = 4; img.sn = (long)Hn * Wn * 4;
-        if (!spec && !c->dry) c->ck(fid_stage_launch(frames, N, H, W, img.p, Hn, Wn, c->stream), "fid stage");
+        if (!spec && !c->dry) c->ck(fid_stage_launch(frames, N, H, W, img.p, Hn, Wn, c->stream, flavour == FLAVOUR_FID), "fid stage");
         mark(1);
         const int h1 = igemm_out(Hn, 3, 2, 0), w1 = igemm_out(Wn, 3, 2, 0), h2 = h1 - 2, w2 = w1 - 2, h3 = (h2 - 3) / 2 + 1, w3 = (w2 - 3) / 2 + 1;
         const int h4 = h3 - 2, w4 = w3 - 2, h35 = (h4 - 3) / 2 + 1, w35 = (w4 - 3) / 2 + 1, h17 = (h35 - 3) / 2 + 1, w17 = (w35 - 3) / 2 + 1, h8 = (h17 - 3) / 2 + 1, w8 = (w17 - 3) / 2 + 1;
@@ -466,42 +505,76 @@ struct FidWalk {
         mark(4);
         // block 3 (inception.py:116-122)
         a = make(P[0], N, h8, w8, 1280); blockD("Mixed_7a", tap2, a); release();
-        b = make(P[1], N, h8, w8, 2048); blockE("Mixed_7b", a, 1, b); release();
-        a = make(P[0], N, h8, w8, 2048); blockE("Mixed_7c", b, 2, a); release();
+        b = make(P[1], N, h8, w8, 2048); blockE("Mixed_7b", a, avg_mode(), b); release();
+        a = make(P[0], N, h8, w8, 2048); blockE("Mixed_7c", b, flavour == FLAVOUR_TV ? 3 : 2, a); release();
         if (!spec && !c->dry) c->ck(fid_global_avg_launch(tv(a), F->feat, c->stream), "fid global average");
         mark(5);
+        if (flavour == FLAVOUR_TV) {      // torchvision's tail: dropout is the identity in eval mode, then fc and (inception_score.py:43) the softmax
+            const bool live = !spec && !c->dry;
+            if (live) hipLaunchKernelGGL(k_fid_d2f, dim3(grid_for((long)N * FID_DIM)), dim3(256), 0, c->stream, (const double*)F->feat, F->feat32, (long)N * FID_DIM);
+            FMap pooled = make(spec ? nullptr : F->feat32, N, 1, 1, FID_DIM), lg = make(spec ? nullptr : F->logits, N, 1, 1, IS_CLASSES);
+            conv("fc", pooled, IS_CLASSES, 1, 1, 1, 0, 0, &lg, 1);
+            if (live) c->ck(is_softmax_launch(F->logits, F->probs, N, IS_CLASSES, IS_CLASSES, IS_CLASSES, c->stream), "is softmax");
+            mark(6);
+        }
         if (!spec && !c->dry && F->timed) F->timed_ran = true;
         if (!spec) { F->taps[0] = tv(tap0); F->taps[1] = tv(tap1); F->taps[2] = tv(tap2); F->last_nf = N; }
     }
 };
 
-const std::vector<FidSpec>& fid_specs() {
-    static std::vector<FidSpec> S;
-    if (S.empty()) { FidWalk w; w.spec = &S; w.run(nullptr, 1, 299, 299, 299, 299); }
-    return S;
+const std::vector<FidSpec>& fid_specs(int flavour = FLAVOUR_FID) {
+    static std::vector<FidSpec> S[2];
+    if (S[flavour].empty()) { FidWalk w; w.spec = &S[flavour]; w.flavour = flavour; w.run(nullptr, 1, 299, 299, 299, 299); }
+    return S[flavour];
 }
 const char* const FID_LEAVES[5] = {"conv.weight", "bn.weight", "bn.bias", "bn.running_mean", "bn.running_var"};
-long fid_layer_floats(const FidSpec& s) { return (long)s.cout * s.cin * s.kh * s.kw + 4L * s.cout; }
+const char* const FC_LEAVES[2] = {"weight", "bias"};
+inline int fid_layer_leaves(const FidSpec& s) { return s.linear ? 2 : 5; }
+long fid_layer_floats(const FidSpec& s) { return (long)s.cout * s.cin * s.kh * s.kw + (s.linear ? 1L : 4L) * s.cout; }
+int fid_param_count(int flavour) { int n = 0; for (const FidSpec& s : fid_specs(flavour)) n += fid_layer_leaves(s); return n; }
+long fid_param_floats(int flavour) { long n = 0; for (const FidSpec& s : fid_specs(flavour)) n += fid_layer_floats(s); return n; }
+int fid_param_info(int flavour, int index, caddy_param_info* out) {
+    if (index < 0 || !out) return -1;
+    long off = 0;
+    for (const FidSpec& s : fid_specs(flavour)) {
+        const int leaves = fid_layer_leaves(s);
+        if (index >= leaves) { index -= leaves; off += fid_layer_floats(s); continue; }
+        const long nw = (long)s.cout * s.cin * s.kh * s.kw;
+        memset(out, 0, sizeof(*out));
+        snprintf(out->name, sizeof(out->name), "%s.%s", s.name, s.linear ? FC_LEAVES[index] : FID_LEAVES[index]);
+        out->kind = 3;
+        out->shape[0] = s.cout; out->shape[1] = out->shape[2] = out->shape[3] = 1;
+        if (index == 0) {
+            out->offset = off; out->shape[1] = s.cin;
+            if (s.linear) out->ndim = 2; else { out->ndim = 4; out->shape[2] = s.kh; out->shape[3] = s.kw; }
+        } else { out->offset = off + nw + (long)(index - 1) * s.cout; out->ndim = 1; }
+        return 0;
+    }
+    return -1;
+}
 
-bool fid_args_ok(int max_frames, int H, int W, int resize) {
-    if (max_frames < 1 || H < 1 || W < 1) { set_error("caddy_fid: max_frames, height and width must be positive"); return false; }
-    if (!resize && (H < 75 || W < 75)) { set_error("caddy_fid: without the 299 x 299 resize the Inception trunk needs frames of at least 75 x 75"); return false; }
+bool fid_args_ok(int max_frames, int H, int W, int resize, const char* who = "caddy_fid") {
+    if (max_frames < 1 || H < 1 || W < 1) { set_error(std::string(who) + ": max_frames, height and width must be positive"); return false; }
+    if (!resize && (H < 75 || W < 75)) { set_error(std::string(who) + ": without the 299 x 299 resize the Inception trunk needs frames of at least 75 x 75"); return false; }
     return true;
 }
 void fid_chunk(caddy_ctx* c, const float* frames, int nf) {
-    FidWalk w; w.c = c; w.F = c->fid;
+    FidWalk w; w.c = c; w.F = c->fid; w.flavour = c->fid->flavour;
     w.run(frames, nf, c->cfg.height, c->cfg.width, c->fid->Hn, c->fid->Wn);
 }
 const char* const FID_SIZER = "caddy_fid_workspace_bytes";
-// FID kind (caddy_fid_ctx_create): both packed forms and the folded bias of every Inception layer, 2048 feature doubles per frame; the activation arena of one chunk of the walk
-EvalKind fid_kind(int max_frames, int H, int W, int resize) {
-    return {CTX_FID, max_frames, H, W,
+const char* const IS_SIZER = "caddy_is_workspace_bytes";
+// FID kind (caddy_fid_ctx_create): both packed forms and the folded bias of every Inception layer, 2048 feature doubles per frame; the activation arena of one chunk of the walk.
+// IS kind (caddy_is_ctx_create): the same with the torchvision flavour of the walk, its fc layer, and per frame the narrowed features, 1000 logits and 1000 probabilities.
+EvalKind fid_kind(int max_frames, int H, int W, int resize, int flavour = FLAVOUR_FID) {
+    return {flavour == FLAVOUR_TV ? CTX_IS : CTX_FID, max_frames, H, W,
             [=](caddy_ctx* c) {
                 FidState* F = new FidState();
                 c->fid = F;
+                F->flavour = flavour;
                 F->resize = resize ? 1 : 0; F->Hn = resize ? 299 : H; F->Wn = resize ? 299 : W;
                 long off = 0;
-                for (const FidSpec& s : fid_specs()) {
+                for (const FidSpec& s : fid_specs(flavour)) {
                     FidLayer L; L.s = s; L.off = off; off += fid_layer_floats(s);
                     const size_t wb = igemm_weight_bytes(s.cin, s.cout, s.kh, s.kw);
                     L.w32 = c->persist.alloc(wb); L.w16 = c->persist.alloc(wb);
@@ -509,14 +582,68 @@ EvalKind fid_kind(int max_frames, int H, int W, int resize) {
                     F->L.push_back(L);
                 }
                 F->feat = (double*)c->persist.alloc(sizeof(double) * FID_DIM * (size_t)max_frames);
+                if (flavour == FLAVOUR_TV) {
+                    F->feat32 = (float*)c->persist.alloc(sizeof(float) * FID_DIM * (size_t)max_frames);
+                    F->logits = (float*)c->persist.alloc(sizeof(float) * IS_CLASSES * (size_t)max_frames);
+                    F->probs = (float*)c->persist.alloc(sizeof(float) * IS_CLASSES * (size_t)max_frames);
+                }
             },
             [=](caddy_ctx* c) { fid_chunk(c, nullptr, max_frames); },
-            FID_SIZER};
+            flavour == FLAVOUR_TV ? IS_SIZER : FID_SIZER};
 }
-bool fid_ctx_ok(caddy_ctx* c, const char* who) {
-    if (!ctx_needs(c, CTX_FID, who)) return false;
+bool fid_ctx_ok(caddy_ctx* c, const char* who, int kind = CTX_FID) {
+    if (!ctx_needs(c, kind, who)) return false;
     c->fail = false;
     return true;
+}
+caddy_ctx* fid_env(caddy_ctx* c) {      // CADDY_PRECISION of the environment, read once when a context is created (c null: creation failed)
+    if (c) if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) c->fid->precision = PREC_FP32;
+    return c;
+}
+int fid_load(caddy_ctx* c, const float* flat, const char* sizer) {
+    if (!flat) { set_error("null input"); return -2; }
+    for (FidLayer& L : c->fid->L) {
+        const FidSpec& s = L.s;
+        const float* w = flat + L.off;
+        const float* bn = w + (long)s.cout * s.cin * s.kh * s.kw;      // the four BatchNorm vectors, or fc's bias
+        if (s.linear) c->ck(igemm_pack(w, nullptr, nullptr, nullptr, nullptr, 0.f, bn, s.cin, s.cout, s.kh, s.kw, L.w32, L.w16, L.bias, c->stream), s.name);
+        else c->ck(igemm_pack(w, bn, bn + s.cout, bn + 2 * s.cout, bn + 3 * s.cout, FID_EPS, nullptr, s.cin, s.cout, s.kh, s.kw, L.w32, L.w16, L.bias, c->stream), s.name);
+    }
+    hipStreamSynchronize(c->stream);      // the caller's buffer is not referenced after this call
+    c->fid->loaded = !c->fail;
+    return finish(c, sizer);
+}
+int fid_set_precision(caddy_ctx* c, int forward, const char* who) {
+    if (forward != PREC_FP32 && forward != PREC_F16X3) { set_error(std::string(who) + ": 0 (exact fp32) | 16 (split f16)"); return -2; }
+    c->fid->precision = forward;
+    return 0;
+}
+// every chunk of n frames through the walk; a layer of the split-f16 path that left the f16 range moves to exact fp32 and the chunk runs again.  copy(n0, nf) fetches a chunk's result.
+template <class Copy> void fid_run_chunks(caddy_ctx* c, const float* frames, int n, Copy copy) {
+    FidState* F = c->fid;
+    const long fr = 3L * c->cfg.height * c->cfg.width;
+    for_chunks(c, n, [&](long n0, int nf) {      // (the activation arena holds max_frames frames)
+        for (int attempt = 0; attempt < 2; attempt++) {
+            fid_chunk(c, frames + n0 * fr, nf);
+            if (c->fail) return false;
+            if (F->precision == PREC_FP32 || !range_guard_retry(c, 0, (int)F->L.size())) break;
+        }
+        copy(n0, nf);
+        hipStreamSynchronize(c->stream);
+        return true;
+    });
+}
+int fid_stage_ms(caddy_ctx* c, int on, float* ms, int stages, const char* who) {
+    FidState* F = c->fid;
+    if (ms) {
+        if (!F->timed_ran) { set_error(std::string(who) + ": no timed chunk has run"); return -2; }
+        hipStreamSynchronize(c->stream);
+        for (int k = 0; k < stages; k++) hipEventElapsedTime(ms + k, F->ev[k], F->ev[k + 1]);
+    }
+    if (on && !F->ev[0]) for (hipEvent_t& e : F->ev) hipEventCreate(&e);
+    F->timed = on != 0;
+    if (!on) F->timed_ran = false;
+    return 0;
 }
 }  // namespace
 
@@ -532,45 +659,18 @@ size_t caddy_fid_workspace_bytes(int max_frames, int height, int width, int resi
     return fid_args_ok(max_frames, height, width, resize) ? eval_workspace_bytes(fid_kind(max_frames, height, width, resize)) : 0;
 }
 caddy_ctx* caddy_fid_ctx_create(int max_frames, int height, int width, int resize, void* workspace, size_t bytes) {
-    caddy_ctx* c = fid_args_ok(max_frames, height, width, resize) ? eval_ctx_create(fid_kind(max_frames, height, width, resize), workspace, bytes) : nullptr;
-    if (c) if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) c->fid->precision = PREC_FP32;
-    return c;
+    return fid_args_ok(max_frames, height, width, resize) ? fid_env(eval_ctx_create(fid_kind(max_frames, height, width, resize), workspace, bytes)) : nullptr;
 }
-int caddy_fid_param_count(void) { return 5 * (int)fid_specs().size(); }
-long caddy_fid_param_floats(void) { long n = 0; for (const FidSpec& s : fid_specs()) n += fid_layer_floats(s); return n; }
-int caddy_fid_param_info_get(int index, caddy_param_info* out) {
-    const std::vector<FidSpec>& S = fid_specs();
-    if (index < 0 || index >= 5 * (int)S.size() || !out) return -1;
-    long off = 0;
-    for (int i = 0; i < index / 5; i++) off += fid_layer_floats(S[i]);
-    const FidSpec& s = S[index / 5];
-    const int leaf = index % 5;
-    const long nw = (long)s.cout * s.cin * s.kh * s.kw;
-    memset(out, 0, sizeof(*out));
-    snprintf(out->name, sizeof(out->name), "%s.%s", s.name, FID_LEAVES[leaf]);
-    out->kind = 3;
-    if (leaf == 0) { out->offset = off; out->ndim = 4; out->shape[0] = s.cout; out->shape[1] = s.cin; out->shape[2] = s.kh; out->shape[3] = s.kw; }
-    else { out->offset = off + nw + (long)(leaf - 1) * s.cout; out->ndim = 1; out->shape[0] = s.cout; out->shape[1] = out->shape[2] = out->shape[3] = 1; }
-    return 0;
-}
+int caddy_fid_param_count(void) { return fid_param_count(FLAVOUR_FID); }
+long caddy_fid_param_floats(void) { return fid_param_floats(FLAVOUR_FID); }
+int caddy_fid_param_info_get(int index, caddy_param_info* out) { return fid_param_info(FLAVOUR_FID, index, out); }
 int caddy_load_fid_inception(caddy_ctx* c, const float* flat) {
     if (!fid_ctx_ok(c, "caddy_load_fid_inception")) return -2;
-    if (!flat) { set_error("null input"); return -2; }
-    for (FidLayer& L : c->fid->L) {
-        const FidSpec& s = L.s;
-        const float* w = flat + L.off;
-        const float* bn = w + (long)s.cout * s.cin * s.kh * s.kw;
-        c->ck(igemm_pack(w, bn, bn + s.cout, bn + 2 * s.cout, bn + 3 * s.cout, FID_EPS, nullptr, s.cin, s.cout, s.kh, s.kw, L.w32, L.w16, L.bias, c->stream), s.name);
-    }
-    hipStreamSynchronize(c->stream);      // the caller's buffer is not referenced after this call
-    c->fid->loaded = !c->fail;
-    return finish(c, FID_SIZER);
+    return fid_load(c, flat, FID_SIZER);
 }
 int caddy_set_fid_precision(caddy_ctx* c, int forward) {
     if (!fid_ctx_ok(c, "caddy_set_fid_precision")) return -2;
-    if (forward != PREC_FP32 && forward != PREC_F16X3) { set_error("caddy_set_fid_precision: 0 (exact fp32) | 16 (split f16)"); return -2; }
-    c->fid->precision = forward;
-    return 0;
+    return fid_set_precision(c, forward, "caddy_set_fid_precision");
 }
 int caddy_fid_features(caddy_ctx* c, const float* frames, int n, double* out_host) {
     if (!fid_ctx_ok(c, "caddy_fid_features")) return -2;
@@ -578,18 +678,7 @@ int caddy_fid_features(caddy_ctx* c, const float* frames, int n, double* out_hos
     if (n < 1) { set_error("caddy_fid_features: n must be positive"); return -2; }
     FidState* F = c->fid;
     if (!F->loaded) { set_error("caddy_fid_features: no Inception weights were loaded (caddy_load_fid_inception)"); return -2; }
-    const long fr = 3L * c->cfg.height * c->cfg.width;
-    for_chunks(c, n, [&](long n0, int nf) {      // (the activation arena holds max_frames frames)
-        // a layer of the split-f16 path that left the f16 range moves to exact fp32 and the chunk runs again
-        for (int attempt = 0; attempt < 2; attempt++) {
-            fid_chunk(c, frames + n0 * fr, nf);
-            if (c->fail) return false;
-            if (F->precision == PREC_FP32 || !range_guard_retry(c, 0, (int)F->L.size())) break;
-        }
-        hipMemcpyAsync(out_host + n0 * FID_DIM, F->feat, sizeof(double) * FID_DIM * nf, hipMemcpyDeviceToHost, c->stream);
-        hipStreamSynchronize(c->stream);
-        return true;
-    });
+    fid_run_chunks(c, frames, n, [&](long n0, int nf) { hipMemcpyAsync(out_host + n0 * FID_DIM, F->feat, sizeof(double) * FID_DIM * nf, hipMemcpyDeviceToHost, c->stream); });
     return finish(c, FID_SIZER);
 }
 int caddy_debug_fid_block(caddy_ctx* c, int block, float* dst_nchw) {
@@ -605,16 +694,7 @@ int caddy_debug_fid_fallback_layers(caddy_ctx* c) { return (c && c->kind == CTX_
 /* on: the next chunks record events at the stage boundaries; ms5 (nullable) receives resize, stem, 35 x 35, 17 x 17 and 8 x 8 times of the LAST chunk */
 int caddy_debug_fid_stage_ms(caddy_ctx* c, int on, float* ms5) {
     if (!fid_ctx_ok(c, "caddy_debug_fid_stage_ms")) return -2;
-    FidState* F = c->fid;
-    if (ms5) {
-        if (!F->timed_ran) { set_error("caddy_debug_fid_stage_ms: no timed chunk has run"); return -2; }
-        hipStreamSynchronize(c->stream);
-        for (int k = 0; k < 5; k++) hipEventElapsedTime(ms5 + k, F->ev[k], F->ev[k + 1]);
-    }
-    if (on && !F->ev[0]) for (hipEvent_t& e : F->ev) hipEventCreate(&e);
-    F->timed = on != 0;
-    if (!on) F->timed_ran = false;
-    return 0;
+    return fid_stage_ms(c, on, ms5, 5, "caddy_debug_fid_stage_ms");
 }
 double caddy_fid_macs_per_frame(int height, int width, int resize) {
     std::vector<FidSpec> S; FidWalk w; w.spec = &S;
@@ -630,4 +710,52 @@ int caddy_k_conv_igemm(const IgemmArgs* a, void* stream) { return igemm_launch(*
 int caddy_k_fid_pool(const TV* in, const TV* out, int mode, void* stream) { return fid_pool_launch(*in, *out, mode, (hipStream_t)stream); }
 int caddy_k_fid_global_avg(const TV* in, double* out, void* stream) { return fid_global_avg_launch(*in, out, (hipStream_t)stream); }
 int caddy_k_fid_stage(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, void* stream) { return fid_stage_launch(src, n, Hs, Ws, out, Ho, Wo, (hipStream_t)stream); }
+
+// ---- Inception Score (evaluation/metrics/inception_score.py): the IS context and its entry points ----
+size_t caddy_is_workspace_bytes(int max_frames, int height, int width, int resize) {
+    return fid_args_ok(max_frames, height, width, resize, "caddy_is") ? eval_workspace_bytes(fid_kind(max_frames, height, width, resize, FLAVOUR_TV)) : 0;
+}
+caddy_ctx* caddy_is_ctx_create(int max_frames, int height, int width, int resize, void* workspace, size_t bytes) {
+    return fid_args_ok(max_frames, height, width, resize, "caddy_is") ? fid_env(eval_ctx_create(fid_kind(max_frames, height, width, resize, FLAVOUR_TV), workspace, bytes)) : nullptr;
+}
+int caddy_is_param_count(void) { return fid_param_count(FLAVOUR_TV); }
+long caddy_is_param_floats(void) { return fid_param_floats(FLAVOUR_TV); }
+int caddy_is_param_info_get(int index, caddy_param_info* out) { return fid_param_info(FLAVOUR_TV, index, out); }
+int caddy_load_is_inception(caddy_ctx* c, const float* flat) {
+    if (!fid_ctx_ok(c, "caddy_load_is_inception", CTX_IS)) return -2;
+    return fid_load(c, flat, IS_SIZER);
+}
+int caddy_set_is_precision(caddy_ctx* c, int forward) {
+    if (!fid_ctx_ok(c, "caddy_set_is_precision", CTX_IS)) return -2;
+    return fid_set_precision(c, forward, "caddy_set_is_precision");
+}
+int caddy_is_probabilities(caddy_ctx* c, const float* frames, int n, float* out_host) {
+    if (!fid_ctx_ok(c, "caddy_is_probabilities", CTX_IS)) return -2;
+    if (!frames || !out_host) { set_error("null input"); return -2; }
+    if (n < 1) { set_error("caddy_is_probabilities: n must be positive"); return -2; }
+    FidState* F = c->fid;
+    if (!F->loaded) { set_error("caddy_is_probabilities: no Inception weights were loaded (caddy_load_is_inception)"); return -2; }
+    fid_run_chunks(c, frames, n, [&](long n0, int nf) { hipMemcpyAsync(out_host + n0 * IS_CLASSES, F->probs, sizeof(float) * IS_CLASSES * nf, hipMemcpyDeviceToHost, c->stream); });
+    return finish(c, IS_SIZER);
+}
+int caddy_debug_is_logits(caddy_ctx* c, float* dst) {
+    if (!fid_ctx_ok(c, "caddy_debug_is_logits", CTX_IS)) return -2;
+    FidState* F = c->fid;
+    if (!dst || F->last_nf < 1) { set_error("caddy_debug_is_logits: needs a context that has run caddy_is_probabilities"); return -2; }
+    hipMemcpyAsync(dst, F->logits, sizeof(float) * IS_CLASSES * F->last_nf, hipMemcpyDeviceToDevice, c->stream);
+    hipStreamSynchronize(c->stream);
+    return finish(c, IS_SIZER);
+}
+int caddy_debug_is_fallback_layers(caddy_ctx* c) { return (c && c->kind == CTX_IS) ? c->n_fallback : -1; }
+int caddy_debug_is_stage_ms(caddy_ctx* c, int on, float* ms6) {
+    if (!fid_ctx_ok(c, "caddy_debug_is_stage_ms", CTX_IS)) return -2;
+    return fid_stage_ms(c, on, ms6, 6, "caddy_debug_is_stage_ms");
+}
+double caddy_is_macs_per_frame(int height, int width, int resize) {
+    std::vector<FidSpec> S; FidWalk w; w.spec = &S; w.flavour = FLAVOUR_TV;
+    w.run(nullptr, 1, height, width, resize ? 299 : height, resize ? 299 : width);
+    return w.macs;
+}
+int caddy_k_is_stage(const float* src, int n, int Hs, int Ws, float* out, int Ho, int Wo, void* stream) { return fid_stage_launch(src, n, Hs, Ws, out, Ho, Wo, (hipStream_t)stream, 0); }
+int caddy_k_is_softmax(const float* logits, float* probs, int n, int C, long ld_in, long ld_out, void* stream) { return is_softmax_launch(logits, probs, n, C, ld_in, ld_out, (hipStream_t)stream); }
 }

@@ -1705,7 +1705,7 @@ long caddy_vgg_param_floats(void) { return vgg_param_floats(); }
 int caddy_load_vgg(caddy_ctx* c, const float* vgg_flat) {
     c->fail = false;
     if (!vgg_flat) { set_error("null input"); return -2; }
-    if (c->kind & (CTX_LPIPS | CTX_FID)) { set_error("caddy_load_vgg: the context is an LPIPS context (use caddy_load_lpips)"); return -2; }
+    if (c->kind & (CTX_LPIPS | CTX_FID | CTX_IS)) { set_error("caddy_load_vgg: the context is an LPIPS context (use caddy_load_lpips)"); return -2; }
     return vgg_load(c, vgg_flat);
 }
 int caddy_set_perceptual_prefetch(caddy_ctx* c, int on) { c->perc_prefetch = on != 0; return 0; }

@@ -67,7 +67,8 @@ enum { CTX_MODEL = 1,       // caddy_ctx_create
        CTX_METRICS = 2,     // caddy_metrics_ctx_create
        CTX_LPIPS = 4,       // caddy_lpips_ctx_create
        CTX_FID = 8,         // caddy_fid_ctx_create
-       CTX_FVD = 16 };      // caddy_fvd_ctx_create
+       CTX_FVD = 16,        // caddy_fvd_ctx_create
+       CTX_IS = 32 };       // caddy_is_ctx_create (fid.hip: the FID state with the torchvision flavour of the graph)
 
 struct BNL;
 #define CADDY_N_FLAGS 128
@@ -249,7 +250,7 @@ struct caddy_ctx {
     int kind = CTX_MODEL;
     double* fm_slab = nullptr;       // per (frame, tile) partials of the fused pass (cfg.batch = max_frames frames)
     double* fm_out = nullptr;        // CADDY_FM_COUNT x max_frames results of the current chunk
-    struct FidState* fid = nullptr;  // FID feature network (caddy_fid_ctx_create; fid.hip owns it)
+    struct FidState* fid = nullptr;  // FID feature network (caddy_fid_ctx_create) or the Inception Score's classifier (caddy_is_ctx_create); fid.hip owns it
     struct FvdState* fvd = nullptr;  // FVD feature network (caddy_fvd_ctx_create; fvd.hip owns it)
 
     // ---- optional per-launch timing of the conv kernels (HIP events on the launch stream; bench.py roofline) ----

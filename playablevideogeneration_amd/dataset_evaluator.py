@@ -10,7 +10,10 @@ default true, is InceptionV3's resize_input) `fid` is added (evaluation/metrics/
 loop (the reference makes two further passes over each loader), the statistics and the Frechet distance are host fp64.  With I3D weights (`evaluation.fvd_i3d_weights`:
 metrics.find_fvd_weights; `evaluation.fvd_resize_input`, default true, is the 224 x 224 resize of evaluation/metrics/fvd.py:49-56) `fvd` is added (fvd.py:229-330): the I3D logits of
 the sequences are collected inside the same loop, and as IncrementalFVD feeds I3D 16 sequences at a time and drops the incomplete tail, only the first 16 floor(n / 16) sequences of
-each dataset enter the statistics (fewer than 16 raise).  IS and the plots are not computed.  The per-dataset evaluators that add the detection and action metrics of Breakout and BAIR are
+each dataset enter the statistics (fewer than 16 raise).  With torchvision Inception weights (`evaluation.is_inception_weights`: metrics.find_is_weights; `evaluation.is_splits`,
+default 1; `evaluation.is_resize_input`, default true as the reference always resizes, false only for small test geometries) `is/mean` and `is/std` are added
+(evaluation/metrics/inception_score.py:24-65, whose call the reference has commented out at dataset_evaluator.py:74): the class probabilities of the generated dataset's frames are
+collected inside the same loop and the score is host fp64.  The plots are not computed.  The per-dataset evaluators that add the detection and action metrics of Breakout and BAIR are
 dataset_evaluator_breakout and dataset_evaluator_bair (ActionSpaceEvaluator below).
 """
 from typing import Dict
@@ -57,6 +60,12 @@ class DatasetEvaluator:
         self._fvd_embeddings = ([], [])
         if self.fvd_state is None:
             self.logger.print("- fvd skipped: no I3D weights configured (evaluation.fvd_i3d_weights)")
+        self.is_state = M.find_is_weights(config["evaluation"])
+        self.is_splits = int(config["evaluation"].get("is_splits", 1))
+        self.is_resize = bool(config["evaluation"].get("is_resize_input", True))
+        self._is_probabilities = []
+        if self.is_state is None:
+            self.logger.print("- is skipped: no Inception weights configured (evaluation.is_inception_weights)")
         self.logger.print(self.NOT_COMPUTED)
         if self.lpips_state is not None:
             self.logger.print("- lpips is computed (LPIPS weights configured): the line above applies to it no longer")
@@ -64,6 +73,8 @@ class DatasetEvaluator:
             self.logger.print("- fid is computed (Inception weights configured): the line above applies to it no longer")
         if self.fvd_state is not None:
             self.logger.print("- fvd is computed (I3D weights configured): the line above applies to it no longer")
+        if self.is_state is not None:
+            self.logger.print("- is is computed (Inception weights configured): the line above applies to it no longer")
 
     @staticmethod
     def check_range(values: Dict[str, torch.Tensor], which: str):
@@ -124,6 +135,20 @@ class DatasetEvaluator:
         self._fvd_embeddings = ([], [])
         return {"fvd": float(M.fvd_from_embeddings(ref[:M.fvd_batched_count(len(ref))], gen[:M.fvd_batched_count(len(gen))]))}
 
+    def collect_is_probabilities(self, generated_observations: torch.Tensor) -> None:
+        """class probabilities of this batch's generated frames, sequence after sequence (evaluation/metrics/inception_score.py:34-46); nothing without weights"""
+        if self.is_state is None:
+            return
+        self._is_probabilities.append(M.inception_probabilities(generated_observations, self.is_state, resize=self.is_resize).numpy())
+
+    def is_results(self) -> Dict:
+        """{"is/mean", "is/std"} over the probabilities collected since the last call (evaluation/metrics/inception_score.py:48-65); {} without weights"""
+        if self.is_state is None:
+            return {}
+        probs = np.concatenate(self._is_probabilities, axis=0)
+        self._is_probabilities = []
+        return M.inception_score_from_probabilities(probs, self.is_splits)
+
     def metric_names(self, names):
         return [m for m in names if m != "vgg_sim" or self.vgg_state is not None] + (["lpips"] if self.lpips_state is not None else [])
 
@@ -143,11 +168,13 @@ class DatasetEvaluator:
                     acc[m].append(values[m].numpy())
                 self.collect_fid_features(reference_observations, generated_observations)
                 self.collect_fvd_embeddings(reference_observations, generated_observations)
+                self.collect_is_probabilities(generated_observations)
         results = {}
         for m in names:
             results.update(self.compute_positional_statistics(np.concatenate(acc[m], axis=0), m))
         results.update(self.fid_results())
         results.update(self.fvd_results())
+        results.update(self.is_results())
         return results
 
 
@@ -206,6 +233,7 @@ class ActionSpaceEvaluator(DatasetEvaluator):
                     acc[m].append(values[m].numpy())
                 self.collect_fid_features(reference_observations, generated_observations)
                 self.collect_fvd_embeddings(reference_observations, generated_observations)
+                self.collect_is_probabilities(generated_observations)
                 found = self.detect(reference_observations, generated_observations)
                 for k, v in found.items():
                     detections.setdefault(k, []).append(v)
@@ -225,6 +253,7 @@ class ActionSpaceEvaluator(DatasetEvaluator):
         results.update(accuracy)
         results.update(self.fid_results())
         results.update(self.fvd_results())
+        results.update(self.is_results())
         return results
 
 

@@ -20,7 +20,12 @@ LPIPS needs its weights from the caller (a torchvision vgg16 state dict plus the
                                                                                                           pools and legacy bilinear input stage of csrc/fvd.hip; the same host
                                                                                                           fp64 statistics and Frechet distance as FID
 FVD needs the variables of the I3D module from the caller (fvd_i3d_state; INTEGRATION.md has the export recipe): nothing is downloaded.
-(The Inception Score and the Tennis detector stay out of scope.)"""
+    inception_score             evaluation/metrics/inception_score.py:17-65 (torchvision inception_v3 softmax)  -- the same Inception-v3 graph in its torchvision flavour (no input
+                                                                                                          normalisation, padding-including average pools), fc as a 1 x 1
+                                                                                                          implicit-GEMM convolution and the wave-per-frame softmax of csrc/fid.hip;
+                                                                                                          the split KL score in fp64 on the host
+The Inception Score needs a torchvision inception_v3 state dict from the caller (is_inception_state): nothing is downloaded.
+(The Tennis detector and the plots stay out of scope.)"""
 import ctypes as C
 import re
 from typing import Dict, Optional
@@ -43,7 +48,7 @@ def psnr(reference_observations: torch.Tensor, generated_observations: torch.Ten
 SLOTS = ("mse", "motion_masked_mse", "psnr", "ssim", "vgg_sim", "ref_min", "ref_max", "gen_min", "gen_max")      # CADDY_FM_* of include/caddy_hip.h
 VGG_FRAMES_256 = 30      # frames per VGG19 chunk at 256 x 256 (scaled by the frame area): ~4 GB of feature maps
 _default_lib = None
-_contexts: Dict = {}      # every cached context: (kind, library, device, geometry, weights) -> FrameMetrics | LPIPS | InceptionFeatures | I3DEmbeddings
+_contexts: Dict = {}      # every cached context: (kind, library, device, geometry, weights) -> FrameMetrics | LPIPS | InceptionFeatures | I3DEmbeddings | InceptionProbabilities
 
 
 def set_library(lib) -> None:
@@ -86,6 +91,20 @@ def _bind(lib):
         lib.caddy_debug_fid_stage_ms.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.caddy_fid_macs_per_frame.restype = C.c_double
         lib.caddy_fid_macs_per_frame.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.caddy_is_workspace_bytes.restype = C.c_size_t
+        lib.caddy_is_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.caddy_is_ctx_create.restype = C.c_void_p
+        lib.caddy_is_ctx_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        lib.caddy_is_param_floats.restype = C.c_long
+        lib.caddy_is_param_info_get.argtypes = [C.c_int, C.c_void_p]
+        lib.caddy_load_is_inception.argtypes = [C.c_void_p, C.c_void_p]
+        lib.caddy_set_is_precision.argtypes = [C.c_void_p, C.c_int]
+        lib.caddy_is_probabilities.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        lib.caddy_debug_is_logits.argtypes = [C.c_void_p, C.c_void_p]
+        lib.caddy_debug_is_fallback_layers.argtypes = [C.c_void_p]
+        lib.caddy_debug_is_stage_ms.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.caddy_is_macs_per_frame.restype = C.c_double
+        lib.caddy_is_macs_per_frame.argtypes = [C.c_int, C.c_int, C.c_int]
         lib.caddy_fvd_workspace_bytes.restype = C.c_size_t
         lib.caddy_fvd_workspace_bytes.argtypes = [C.c_int] * 5
         lib.caddy_fvd_ctx_create.restype = C.c_void_p
@@ -576,6 +595,132 @@ def fid(reference_observations: torch.Tensor, generated_observations: torch.Tens
     """FID between two sets of frames in [0, 1] (evaluation/metrics/fid.py:140-159); every frame of every sequence is a sample"""
     return fid_from_features(inception_features(reference_observations, weights, lib, resize).numpy(),
                              inception_features(generated_observations, weights, lib, resize).numpy())
+
+
+# ---- Inception Score (caddy_is_probabilities + the host fp64 score) ----
+IS_CLASSES = 1000
+
+
+def is_param_table(lib=None):
+    """[(name, offset, shape)] of caddy_is_param_info_get: the trunk's tensors under torchvision's names in graph order, then fc.weight and fc.bias"""
+    from . import _lib
+    L = _bind(lib if lib is not None else (_default_lib if _default_lib is not None else _lib.load()))
+    return _param_table(L.caddy_is_param_count, L.caddy_is_param_info_get)
+
+
+def is_inception_state(state_dict: Dict[str, torch.Tensor], lib=None) -> Dict[str, torch.Tensor]:
+    """The tensors of torchvision's inception_v3 (evaluation/metrics/inception_score.py:20) under the names of caddy_is_param_info_get: the trunk and `fc.*`.  Key handling as
+    fid_inception_state (a `module.` / `model.` prefix, a {"state_dict": ...} wrapper); `AuxLogits.*` and `num_batches_tracked` are ignored.  A missing tensor raises
+    CaddyError naming it."""
+    from .engine import CaddyError
+    src = state_dict.get("state_dict", state_dict) if isinstance(state_dict, dict) else state_dict
+    out = {}
+    for name, _, _ in is_param_table(lib):
+        key = next((k for k in (name, "module." + name, "model." + name) if k in src), None)
+        if key is None:
+            raise CaddyError(f"Inception Score weights lack {name}")
+        out[name] = src[key]
+    return out
+
+
+def find_is_weights(cfg) -> Optional[Dict[str, torch.Tensor]]:
+    """config["evaluation"] -> is_inception_state(...) of `is_inception_weights` (a path or a dict); None when it is not configured.  Nothing is downloaded."""
+    src = cfg.get("is_inception_weights", None)
+    if src is None:
+        return None
+    if isinstance(src, str):
+        src = torch.load(src, map_location="cpu", weights_only=True)
+    return is_inception_state(src)
+
+
+class InceptionProbabilities(_EvalContext):
+    """The Inception Score's classifier for frames of height x width: torchvision's inception_v3(transform_input=False).eval() behind the 299 x 299 bilinear resize and the softmax
+    (evaluation/metrics/inception_score.py:20-22,41-43) on csrc/fid.hip.  Calling it on (bs, T, 3, H, W) or (n, 3, H, W) frames in [0, 1] returns an (n, 1000) float32 CPU tensor;
+    more than `max_frames` frames run in chunks.  resize=False runs the network at the frames' own size (at least 75 x 75)."""
+
+    def __init__(self, height: int, width: int, max_frames: int, weights, resize: bool = True, lib=None, device=None):
+        super().__init__(height, width, max_frames, lib, device)
+        self.resize = bool(resize)
+        table = is_param_table(self.lib)
+        state = is_inception_state(weights, self.lib)
+        self._create(self.lib.caddy_is_workspace_bytes, self.lib.caddy_is_ctx_create, int(self.resize))
+        self._load(self.lib.caddy_load_is_inception, self.lib.caddy_is_param_floats(), table, state, "Inception Score", staging="cpu")
+
+    def set_precision(self, forward: int):
+        """arithmetic of the convolutions and of fc: 16 (split f16, default) | 0 (exact fp32)"""
+        self._check(self.lib.caddy_set_is_precision(self.ctx, int(forward)))
+
+    def fallback_layers(self) -> int:
+        return int(self.lib.caddy_debug_is_fallback_layers(self.ctx))
+
+    def __call__(self, observations: torch.Tensor) -> torch.Tensor:
+        o = observations
+        if o.dim() == 5:
+            o = o.reshape((-1,) + tuple(o.shape[2:]))      # every frame of every sequence is a row of all_preds (inception_score.py:39-46)
+        if o.dim() != 4 or o.shape[1] != 3 or tuple(o.shape[2:]) != (self.H, self.W):
+            raise ValueError(f"expected (bs, observations_count, 3, {self.H}, {self.W}) or (n, 3, {self.H}, {self.W}) frames, got {tuple(observations.shape)}")
+        n = int(o.shape[0])
+        o = o.detach().to(self.device, torch.float32).contiguous()
+        out = torch.empty(n, IS_CLASSES, dtype=torch.float32)
+        self._stream()
+        self._check(self.lib.caddy_is_probabilities(self.ctx, o.data_ptr(), n, out.data_ptr()))
+        self.last_frames = (n - 1) % self.max_frames + 1
+        return out
+
+    def logits(self) -> torch.Tensor:
+        """the (frames, 1000) float32 logits of the last chunk of the last call, on the CPU (caddy_debug_is_logits)"""
+        buf = torch.empty(self.last_frames, IS_CLASSES, dtype=torch.float32, device=self.device)
+        self._check(self.lib.caddy_debug_is_logits(self.ctx, buf.data_ptr()))
+        return buf.cpu()
+
+    def stage_times(self, on: bool = True, read: bool = False):
+        """per-stage milliseconds of the last timed chunk (input stage, stem, 35 x 35, 17 x 17, 8 x 8, fc + softmax) when `read`; `on` switches the event recording"""
+        ms = (C.c_float * 6)()
+        self._check(self.lib.caddy_debug_is_stage_ms(self.ctx, int(on), ms if read else None))
+        return list(ms) if read else None
+
+
+def _cached_is(observations: torch.Tensor, weights, lib, resize: bool = True) -> InceptionProbabilities:
+    """the Inception Score context of this library, device, frame geometry and weights (cached like _cached_fid)"""
+    H, W = int(observations.shape[-2]), int(observations.shape[-1])
+    n = int(np.prod(observations.shape[:-3]))
+    lib = lib if lib is not None else _default_lib
+    key = ("is", id(lib), str(observations.device), H, W, bool(resize), id(weights))
+    area = 299 * 299 if resize else H * W
+    want = min(n, max(1, FID_FRAMES_256 * 299 * 299 // area))
+    return _cached(key, weights, lambda: InceptionProbabilities(H, W, min(want, 1024), weights, resize, lib))
+
+
+def inception_probabilities(observations: torch.Tensor, weights, lib=None, resize: bool = True) -> torch.Tensor:
+    """(bs, T, 3, H, W) or (n, 3, H, W) frames in [0, 1] -> (n, 1000) float32 class probabilities (evaluation/metrics/inception_score.py:39-46)"""
+    if weights is None:
+        raise ValueError("the Inception Score needs Inception weights (see is_inception_state)")
+    return _cached_is(observations, weights, lib, resize)(observations)
+
+
+def inception_score_from_probabilities(probs, splits: int = 1) -> Dict[str, float]:
+    """{"is/mean", "is/std"} of evaluation/metrics/inception_score.py:48-65 in host fp64: for each of `splits` parts of N // splits rows (the tail is dropped)
+    exp(mean_i KL(p_i || mean_j p_j)), with scipy.stats.entropy's renormalisation of both arguments; the mean and the population standard deviation over the parts."""
+    p = np.asarray(probs, dtype=np.float64)
+    if p.ndim != 2:
+        raise ValueError(f"expected (n, classes) probabilities, got {p.shape}")
+    n, splits = p.shape[0], int(splits)
+    if splits < 1 or splits > n:
+        raise ValueError(f"inception score: {splits} splits of {n} rows (a part would be empty)")
+    size, scores = n // splits, []
+    for k in range(splits):
+        part = p[k * size:(k + 1) * size]
+        py = part.mean(axis=0)
+        pk, qk = part / part.sum(axis=1, keepdims=True), py / py.sum()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            terms = np.where(pk > 0, pk * np.log(pk / qk), 0.0)      # rel_entr: 0 where p = 0 (q = 0 with p > 0 cannot occur: q is the mean of the p)
+        scores.append(np.exp(terms.sum(axis=1).mean()))
+    return {"is/mean": float(np.mean(scores)), "is/std": float(np.std(scores))}
+
+
+def inception_score(observations: torch.Tensor, weights, splits: int = 1, resize: bool = True, lib=None) -> Dict[str, float]:
+    """Inception Score of frames in [0, 1] (evaluation/metrics/inception_score.py:24-65); every frame of every sequence is a sample"""
+    return inception_score_from_probabilities(inception_probabilities(observations, weights, lib, resize).numpy(), splits)
 
 
 # ---- FVD (caddy_fvd_embeddings + the host fp64 statistics of FID) ----
