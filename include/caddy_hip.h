@@ -362,6 +362,22 @@ int caddy_f16_saturated(caddy_ctx* ctx);
 int caddy_fallback_layers(caddy_ctx* ctx);
 int caddy_generate_next(caddy_ctx* ctx, const float* observation, int action, const float* variation, float* frame_out, float* obs_out);
 
+/* --- batched roll-out: n independent sequences advance per call, each as Model.start_inference / Model.generate_next would advance it alone (model/main_model/model.py:561-607;
+ *     eval-mode BatchNorm is a per-channel affine map, so nothing couples the sequences).  One graph launch per frame whatever n is.
+ *     caddy_start_inference_batch: 1 <= n <= min(caddy_config.batch, 64) (else -2); re-initialises the ConvLSTM memory of sequence slots 0 .. n-1 from the learned initial state,
+ *       prepares the folded inference weights as caddy_start_inference does and drops a graph captured for another n.  caddy_start_inference(ctx) is the n = 1 case.
+ *     caddy_generate_next_batch (-2 before caddy_start_inference_batch):
+ *       observations: (n,3S,H,W) device;  actions: n ints, HOST, each in [0, K) (else -2);  variations: (n,Da) device or NULL (= zeros);
+ *       reset: n bytes, HOST, or NULL -- a non-zero byte re-initialises that sequence's memory before this step (one sequence restarts while the others go on);
+ *       frames_out: (n,3,H,W) device;  obs_out: (n,3S,H,W) device or NULL, per sequence cat[frame, observation[:-3]] (model.py:605).
+ *       observations, frames_out and obs_out are 16-byte aligned and must NOT overlap (rejected with -2, as caddy_generate_next does per buffer).
+ *       The host arrays are read before the call returns.  With n > 1 under way caddy_generate_next returns -2.
+ *     caddy_rollout_copy_state: ConvLSTM (h, c) of all three cells from sequence slot src to slot dst (both in [0, n), else -2) -- a fork: what an all-actions preview
+ *       or a tree of action scripts is built from. --- */
+int caddy_start_inference_batch(caddy_ctx* ctx, int n);
+int caddy_generate_next_batch(caddy_ctx* ctx, const float* observations, const int* actions, const float* variations, const unsigned char* reset, float* frames_out, float* obs_out);
+int caddy_rollout_copy_state(caddy_ctx* ctx, int src, int dst);
+
 /* --- live kernel timing: HIP events recorded on the launch stream around every conv launch between begin and end.
  *     out = CADDY_PROFILE_FAMILIES kernel families (csrc/common.h CK_*: the four k_conv_fwd tilings, k_conv_thin_out, k_conv_thin_in, three
  *             k_conv_wgrad tilings, k_conv_wgrad_small, k_wgrad_thin, k_conv_wgrad_tile, k_conv_narrow, k_conv_hx<128|64|32> on 4 waves, k_wgrad_hx, k_conv_hx<128> on 8 waves)
@@ -384,6 +400,9 @@ int caddy_profile_phases(caddy_ctx* ctx, char* names_out, float* ms_out, int max
 /* --- introspection (debug / tests): the i-th intermediate activation (grad=0) or its gradient (grad=1) of the last
  *     forward, converted to (N,C,H,W) --- */
 int caddy_debug_count(caddy_ctx* ctx);
+/* kernel nodes of the captured per-frame roll-out graph: the launches one graph launch replaces (tools/bench_rollout_batch.py).  0: no graph is captured (the frames run
+ * eagerly, or none has run since caddy_start_inference[_batch]); -1: the count is not available */
+int caddy_debug_rollout_graph_nodes(caddy_ctx* ctx);
 /* BatchNorm fusion bookkeeping since creation: out3 = {train-mode BatchNorm calls, ... whose statistics came from the producing conv's epilogue,
  * ... whose normalised output was never materialised (applied by the consuming convolution)} */
 int caddy_debug_fusion_counts(caddy_ctx* ctx, long* out3);

@@ -57,6 +57,17 @@ struct SmallLossArgs {
 
 int head_rollout_in(const float* obs, float* o_nhwc, int HW, int C, int ld, float* aux, int action, const float* variation, int K, int Da, hipStream_t st);
 int head_rollout_out(const float* f_nhwc, int fld, const float* obs, float* frame_out, float* obs_out, int HW, int C, hipStream_t st);
+// Batched roll-out boundary (head.hip: k_rollout_in_batch / k_rollout_out_batch).  One launch carries up to ROLL_CTL_MAX sequences: their actions and reset flags
+// travel as a kernel argument (no staging copy, nothing to synchronise); caddy_start_inference_batch refuses a larger batch.
+#define ROLL_CTL_MAX 64
+// ConvLSTM state of the roll-out: tensor t (h and c of the three cells) holds one contiguous block of len4[t] float4 per sequence slot, `init[t]` the learned initial state
+struct RollState { const float* init[6]; float* state[6]; int len4[6]; };
+// observations (n, C, HW) planar -> o_nhwc (n, HW, ld); aux row s = [one-hot action[s] (K) | variations[s] (Da) or zeros | zero pad]; state of the slots with reset[s] != 0 <- init.
+// HW a multiple of 4, every pointer 16-byte aligned.
+int head_rollout_in_batch(const float* obs, float* o_nhwc, int n, int HW, int C, int ld, float* aux, const int* actions, const unsigned char* reset, const float* variations,
+                          int K, int Da, const RollState& rs, hipStream_t st);
+// f_nhwc (n, HW, fld; fld must be 4: a pixel is read as one float4) -> frames_out (n, 3, HW); obs_out (n, C, HW) = cat[frame, obs[:-3]] per sequence (nullable)
+int head_rollout_out_batch(const float* f_nhwc, int fld, long f_sn, const float* obs, float* frames_out, float* obs_out, int n, int HW, int C, hipStream_t st);
 int head_softmax(const float* logits, float* prob, float* logp, int NS, int K, hipStream_t st);
 int head_forward(const HeadBufs& h, const HeadParams& p, int B, int T, hipStream_t st);
 int head_sample(const HeadBufs& h, const HeadParams& p, const SampleCfg& c, int NS, float* cen_sums, allreduce_hook_t hook, void* user, const SamplerHooks* sh, hipStream_t st);

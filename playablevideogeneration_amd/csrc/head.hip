@@ -476,6 +476,82 @@ int head_rollout_out(const float* f_nhwc, int fld, const float* obs, float* fram
     hipLaunchKernelGGL(k_rollout_out, dim3(cdiv(HW, 256)), dim3(256), 0, st, f_nhwc, fld, obs, frame_out, obs_out, HW, C);
     return 0;
 }
+// The same two boundaries for n sequences per graph launch (Model.generate_next for a batch of independent roll-outs, model.py:561-607).  Both move whole images -- at
+// n = 16, 256x256, S = 4: 50 MB per frame -- so every access is 16 bytes wide: a thread owns four consecutive pixels of one channel quad, reads them as one float4 per
+// channel plane, transposes 4 x 4 in registers and writes one float4 per pixel (the quad index runs fastest over the lanes: neighbouring lanes complete a pixel's row).
+// k_rollout_in_batch also writes the n auxiliary rows and re-initialises the ConvLSTM state of the flagged slots, so that one sequence can restart while the others go on.
+struct RollCtlDev { int action[ROLL_CTL_MAX]; int rslot[ROLL_CTL_MAX]; int nreset; };
+__global__ __launch_bounds__(256) void k_rollout_in_batch(const float* obs, float* o, int n, int HW, int C, int ld, float* aux, RollCtlDev ctl, const float* variations, int K, int Da,
+                                                          RollState rs, int tot4) {
+    const int HW4 = HW >> 2, Q = ld >> 2;
+    const long img = (long)n * HW4 * Q, naux = (long)n * AUX_LD, total = img + naux + (long)ctl.nreset * tot4;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        if (i < img) {
+            const int q = (int)(i % Q);
+            const long r = i / Q;
+            const int pg = (int)(r % HW4), s = (int)(r / HW4);
+            const float* src = obs + ((long)s * C + 4 * q) * HW + 4 * pg;
+            float4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = 4 * q + k < C ? *reinterpret_cast<const float4*>(src + (long)k * HW) : make_float4(0.f, 0.f, 0.f, 0.f);
+            float* dst = o + ((long)s * HW + 4 * pg) * ld + 4 * q;
+            *reinterpret_cast<float4*>(dst) = make_float4(v[0].x, v[1].x, v[2].x, v[3].x);
+            *reinterpret_cast<float4*>(dst + ld) = make_float4(v[0].y, v[1].y, v[2].y, v[3].y);
+            *reinterpret_cast<float4*>(dst + 2 * ld) = make_float4(v[0].z, v[1].z, v[2].z, v[3].z);
+            *reinterpret_cast<float4*>(dst + 3 * ld) = make_float4(v[0].w, v[1].w, v[2].w, v[3].w);
+        } else if (i < img + naux) {
+            const int j = (int)(i - img), s = j / AUX_LD, e = j - s * AUX_LD;
+            aux[j] = e == ctl.action[s] ? 1.f : ((variations && e >= K && e < K + Da) ? variations[s * Da + e - K] : 0.f);
+        } else {
+            const long j = i - img - naux;
+            const int slot = ctl.rslot[(int)(j / tot4)];
+            int e = (int)(j % tot4), t = 0;
+            while (t < 5 && e >= rs.len4[t]) { e -= rs.len4[t]; t++; }
+            reinterpret_cast<float4*>(rs.state[t])[(long)slot * rs.len4[t] + e] = reinterpret_cast<const float4*>(rs.init[t])[e];
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_rollout_out_batch(const float* f, long f_sn, const float* obs, float* frames_out, float* obs_out, int n, int HW, int C) {
+    const int HW4 = HW >> 2;
+    const long fr = (long)n * HW4, sh4 = obs_out ? (long)(C - 3) * HW4 : 0, total = fr + (long)n * sh4;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        if (i < fr) {
+            const int pg = (int)(i % HW4), s = (int)(i / HW4);
+            const float4* q = reinterpret_cast<const float4*>(f + (long)s * f_sn) + 4 * pg;      // four [r, g, b, pad] pixels
+            const float4 p0 = q[0], p1 = q[1], p2 = q[2], p3 = q[3];
+            const float4 r = make_float4(p0.x, p1.x, p2.x, p3.x), g = make_float4(p0.y, p1.y, p2.y, p3.y), b = make_float4(p0.z, p1.z, p2.z, p3.z);
+            float* fo = frames_out + (long)s * 3 * HW + 4 * pg;
+            *reinterpret_cast<float4*>(fo) = r; *reinterpret_cast<float4*>(fo + HW) = g; *reinterpret_cast<float4*>(fo + 2L * HW) = b;
+            if (obs_out) {
+                float* oo = obs_out + (long)s * C * HW + 4 * pg;
+                *reinterpret_cast<float4*>(oo) = r; *reinterpret_cast<float4*>(oo + HW) = g; *reinterpret_cast<float4*>(oo + 2L * HW) = b;
+            }
+        } else {      // obs_out[s][3:] = obs[s][:-3]: (C - 3) contiguous planes
+            const long j = i - fr;
+            const int s = (int)(j / sh4);
+            const long e = j - (long)s * sh4;
+            reinterpret_cast<float4*>(obs_out + ((long)s * C + 3) * HW)[e] = reinterpret_cast<const float4*>(obs + (long)s * C * HW)[e];
+        }
+    }
+}
+static inline unsigned roll_grid(long items) { return (unsigned)(items < 256L * 8192 ? cdiv(items > 0 ? items : 1, 256) : 8192); }
+int head_rollout_in_batch(const float* obs, float* o_nhwc, int n, int HW, int C, int ld, float* aux, const int* actions, const unsigned char* reset, const float* variations,
+                          int K, int Da, const RollState& rs, hipStream_t st) {
+    if (n < 1 || n > ROLL_CTL_MAX || (HW & 3) || (ld & 3) || ld < C || K + Da > AUX_LD) return -1;      // (one launch carries the actions and reset flags of at most ROLL_CTL_MAX sequences)
+    int tot4 = 0;
+    for (int t = 0; t < 6; t++) tot4 += rs.len4[t];
+    RollCtlDev ctl{};
+    for (int s = 0; s < n; s++) { ctl.action[s] = actions[s]; if (reset && reset[s]) ctl.rslot[ctl.nreset++] = s; }
+    const long items = (long)n * (HW >> 2) * (ld >> 2) + (long)n * AUX_LD + (long)ctl.nreset * tot4;
+    hipLaunchKernelGGL(k_rollout_in_batch, dim3(roll_grid(items)), dim3(256), 0, st, obs, o_nhwc, n, HW, C, ld, aux, ctl, variations, K, Da, rs, tot4);
+    return 0;
+}
+int head_rollout_out_batch(const float* f_nhwc, int fld, long f_sn, const float* obs, float* frames_out, float* obs_out, int n, int HW, int C, hipStream_t st) {
+    if (fld != 4 || (HW & 3) || (f_sn & 3) || C < 3) return -1;      // (the kernel reads a pixel as one float4: [r, g, b, pad])
+    const long items = (long)n * (HW >> 2) * (obs_out ? C - 2 : 1);
+    hipLaunchKernelGGL(k_rollout_out_batch, dim3(roll_grid(items)), dim3(256), 0, st, f_nhwc, f_sn, obs, frames_out, obs_out, n, HW, C);
+    return 0;
+}
 int head_softmax(const float* logits, float* prob, float* logp, int NS, int K, hipStream_t st) {
     hipLaunchKernelGGL(k_softmax_rows, dim3(cdiv(NS, 64)), dim3(64), 0, st, logits, prob, logp, NS, K);
     return 0;

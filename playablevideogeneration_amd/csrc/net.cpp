@@ -242,7 +242,7 @@ void build_layers(caddy_ctx* c) {
         for (int i = 0; i < 3; i++) { c->d_up[i].early_bucket = true; c->d_final[i].early_bucket = true; }
         for (int i = 0; i < 2; i++) { c->d_res[i].conv1.early_bucket = c->d_res[i].conv2.early_bucket = true; if (c->d_res[i].has_down) c->d_res[i].down.early_bucket = true; }
     }
-    c->inf_aux = (float*)c->persist.alloc(AUX_LD * 4);      // roll-out: one-hot action + variation row read by the captured per-frame kernel sequence
+    c->inf_aux = (float*)c->persist.alloc(sizeof(float) * AUX_LD * (size_t)(g.batch > 1 ? g.batch : 1));      // roll-out: one one-hot action + variation row per sequence, read by the captured per-frame kernel sequence
     if (g.perceptual) vgg_build(c);
     for (int i = 0; i < 3; i++) c->d_norm[i].deferred = true;      // D's BatchNorms: their calls execute on two streams (see BNL)
     for (int i = 0; i < 2; i++) { c->d_res[i].bn1.deferred = c->d_res[i].bn2.deferred = true; if (c->d_res[i].has_down) c->d_res[i].bnd.deferred = true; }
@@ -1399,19 +1399,20 @@ static int loss_backward(caddy_ctx* c, const caddy_loss_cfg* lc, double* losses_
     return finish(c);
 }
 
-// Model.generate_next (model/main_model/model.py:570-607), batch 1, eval mode, persistent ConvLSTM state.
-// The per-frame kernel sequence reads the NHWC observation (first allocation of the frame: the same address every frame) and inf_aux and writes the
-// full-resolution frame (NHWC), so that it can be captured once and replayed as one graph launch per frame; one boundary kernel in front of it (the caller's
-// observation -> NHWC, action -> one-hot) and one behind it (frame -> (3, H, W), obs' = cat[frame, observation[:-3]]) are all the data movement there is.
+// Model.generate_next (model/main_model/model.py:570-607) for n independent sequences (n = 1: play.py), eval mode, persistent ConvLSTM state per sequence slot.
+// The per-frame kernel sequence reads the NHWC observations (first allocation of the frame: the same address every frame) and the n rows of inf_aux and writes the
+// full-resolution frames (NHWC), so that it can be captured once per batch extent and replayed as one graph launch per frame; one boundary kernel in front of it (the
+// caller's observations -> NHWC, actions -> one-hot rows, state reset of flagged slots) and one behind it (frames -> (3, H, W), obs' = cat[frame, observation[:-3]]) are
+// all the data movement there is.  Eval-mode BatchNorm is a per-channel affine map: nothing in the body couples the sequences.
 static void rollout_body(caddy_ctx* c, const T4& o) {
     const caddy_config& g = c->cfg;
-    const int H = g.height, W = g.width, K = g.actions, Da = g.action_dim;
+    const int n = o.N, H = g.height, W = g.width, K = g.actions, Da = g.action_dim;
     c->tape.clear(); c->tape2.clear(); c->tp = &c->tape; c->training = false; c->recording = false; c->have_forward = false; c->stats_ring[0] = c->stats_ring[1] = caddy_ctx::TileStats{};
     c->fold = c->packed_fold; c->rollout = true;
     T4 x65 = c->encode(o, false, nullptr);
-    T4 auxv{c->inf_aux, c->inf_aux, 1, 1, 1, K + Da, AUX_LD, AUX_LD};
+    T4 auxv{c->inf_aux, c->inf_aux, n, 1, 1, K + Da, AUX_LD, AUX_LD};
     T4 hdn = c->dynamics(chan(x65, 0, 64), auxv, nullptr);
-    for (int r = 0; r < 3; r++) c->frames[r] = c->alloc(1, H >> r, W >> r, 3);
+    for (int r = 0; r < 3; r++) c->frames[r] = c->alloc(n, H >> r, W >> r, 3);
     c->render(hdn, 0, 1);
     c->roll_frame = c->frames[0];      // (static: the arena is walked in the same order every frame; the boundary kernel behind the graph reads it)
     c->fold = false; c->rollout = false;
@@ -1421,11 +1422,27 @@ void caddy_ctx::drop_graph() {
     if (graph) { hipGraphDestroy(graph); graph = nullptr; }
     graph_valid = false;
 }
-static int generate_next(caddy_ctx* c, const float* observation, int action, const float* variation, float* frame_out, float* obs_out) {
+// kernel nodes of a captured graph (-1: the count is not available; the host simulator has no graph API)
+static int graph_kernel_nodes(hipGraph_t graph) {
+#ifdef HIP_VERSION_MAJOR
+    size_t cnt = 0;
+    if (hipGraphGetNodes(graph, nullptr, &cnt) != hipSuccess) { hipGetLastError(); return -1; }
+    std::vector<hipGraphNode_t> nodes(cnt);
+    if (cnt && hipGraphGetNodes(graph, nodes.data(), &cnt) != hipSuccess) { hipGetLastError(); return -1; }
+    int k = 0;
+    for (size_t i = 0; i < cnt; i++) { hipGraphNodeType t; if (hipGraphNodeGetType(nodes[i], &t) == hipSuccess && t == hipGraphNodeTypeKernel) k++; }
+    return k;
+#else
+    (void)graph; return -1;
+#endif
+}
+// One frame of the n = c->roll_n sequences: `in` (boundary kernel in front of the body; gets the NHWC observation buffer) -> body (graph launch, or eager) -> `out`.
+// (`in` / `out` are the caller's lambdas, taken as template parameters: nothing is allocated per frame)
+template <class In, class Out>
+static int rollout_frame(caddy_ctx* c, const In& in, const Out& out) {
     const caddy_config& g = c->cfg;
-    const int H = g.height, W = g.width, S = g.stacking, K = g.actions, Da = g.action_dim;
+    const int n = c->roll_n, H = g.height, W = g.width, S = g.stacking;
     bool dry = c->dry;
-    if (action < 0 || action >= K) { set_error("action out of range"); return -2; }
     static const int graph_env = getenv("CADDY_ROLLOUT_GRAPH") ? atoi(getenv("CADDY_ROLLOUT_GRAPH")) : 1;      // A/B aid: 0 eager launches, 2 the graph launched on the internal stream (events to / from the caller's stream every frame)
     static const bool graph_off = graph_env == 0;
     hipStream_t user = c->stream;
@@ -1442,9 +1459,13 @@ static int generate_next(caddy_ctx* c, const float* observation, int action, con
     hipStream_t st = on_internal ? c->gstream : user;
     if (on_internal) { hipEventRecord(c->gev_in, user); hipStreamWaitEvent(st, c->gev_in, 0); }
     c->act.reset();
-    T4 o = c->alloc(1, H, W, 3 * S);      // NHWC observation the per-frame kernel sequence reads: first allocation of the frame -> the same address every frame
-    if (!dry) c->ck(head_rollout_in(observation, o.d, H * W, 3 * S, o.ld, c->inf_aux, action, variation, K, Da, st), "observation layout + one-hot action + variation");
+    T4 o = c->alloc(n, H, W, 3 * S);      // NHWC observations the per-frame kernel sequence reads: first allocation of the frame -> the same address every frame
+    if (!dry) c->ck(in(o, st), "observation layout + one-hot action + variation");
     if (graphed) {
+        if (c->graph_valid && c->graph_n != n) {      // (start_inference drops the graph: a graph of another batch extent cannot be met here -- never replay one if it is)
+            hipStreamSynchronize(user); if (c->gstream) hipStreamSynchronize(c->gstream);
+            c->drop_graph();
+        }
         if (!c->graph_valid) {      // first frame after start_inference: capture the kernel sequence (the capture itself executes nothing)
             c->stream = c->gstream;
             bool ok = hipStreamBeginCapture(c->gstream, hipStreamCaptureModeThreadLocal) == hipSuccess;
@@ -1454,15 +1475,42 @@ static int generate_next(caddy_ctx* c, const float* observation, int action, con
                 if (ok) ok = hipGraphInstantiate(&c->graph_exec, c->graph, nullptr, nullptr, 0) == hipSuccess;
             }
             c->stream = user;
-            if (ok) c->graph_valid = true;
+            if (ok) { c->graph_valid = true; c->graph_n = n; c->graph_kernels = graph_kernel_nodes(c->graph); }
             else { c->drop_graph(); c->graph_failed = true; hipGetLastError(); c->fail = false; }
         }
         if (c->graph_valid) { if (hipGraphLaunch(c->graph_exec, st) != hipSuccess) { c->graph_valid = false; c->graph_failed = true; hipGetLastError(); } }
         if (!c->graph_valid) { c->stream = st; rollout_body(c, o); c->stream = user; }      // capture / launch failed: run this frame (and the following ones) eagerly
     } else rollout_body(c, o);
-    if (!dry) c->ck(head_rollout_out(c->roll_frame.d, c->roll_frame.ld, observation, frame_out, obs_out, H * W, 3 * S, st), "frame + next observation");
+    if (!dry) c->ck(out(st), "frame + next observation");
     if (on_internal) { hipEventRecord(c->gev_out, st); hipStreamWaitEvent(user, c->gev_out, 0); }
     return c->fail ? -1 : 0;
+}
+static int generate_next(caddy_ctx* c, const float* observation, int action, const float* variation, float* frame_out, float* obs_out) {
+    const caddy_config& g = c->cfg;
+    const int H = g.height, W = g.width, S = g.stacking, K = g.actions, Da = g.action_dim;
+    if (action < 0 || action >= K) { set_error("action out of range"); return -2; }
+    return rollout_frame(c,
+        [&](const T4& o, hipStream_t st) { return head_rollout_in(observation, o.d, H * W, 3 * S, o.ld, c->inf_aux, action, variation, K, Da, st); },
+        [&](hipStream_t st) { return head_rollout_out(c->roll_frame.d, c->roll_frame.ld, observation, frame_out, obs_out, H * W, 3 * S, st); });
+}
+// ConvLSTM state of the roll-out as the boundary kernel sees it: (h, c) of the three cells, one contiguous block per sequence slot of sn / 4 float4s
+// (caddy_start_inference_batch refuses a state whose sample stride is not a multiple of 4 floats)
+static RollState roll_state(caddy_ctx* c) {
+    RollState rs{};
+    for (int i = 0; i < 3; i++) {
+        LstmL& L = c->lstm[i];
+        rs.init[2 * i] = L.ih.d; rs.state[2 * i] = L.ph.d; rs.len4[2 * i] = (int)(L.ph.sn / 4);
+        rs.init[2 * i + 1] = L.ic.d; rs.state[2 * i + 1] = L.pc.d; rs.len4[2 * i + 1] = (int)(L.pc.sn / 4);
+    }
+    return rs;
+}
+static int generate_next_batch(caddy_ctx* c, const float* observations, const int* actions, const float* variations, const unsigned char* reset, float* frames_out, float* obs_out) {
+    const caddy_config& g = c->cfg;
+    const int n = c->roll_n, H = g.height, W = g.width, S = g.stacking, K = g.actions, Da = g.action_dim;
+    const RollState rs = roll_state(c);
+    return rollout_frame(c,
+        [&](const T4& o, hipStream_t st) { return head_rollout_in_batch(observations, o.d, n, H * W, 3 * S, o.ld, c->inf_aux, actions, reset, variations, K, Da, rs, st); },
+        [&](hipStream_t st) { return head_rollout_out_batch(c->roll_frame.d, c->roll_frame.ld, c->roll_frame.sn, observations, frames_out, obs_out, n, H * W, 3 * S, st); });
 }
 
 // eval-mode affine form of every BatchNorm + the packed weights of the roll-out (BatchNorm folded into the preceding conv unless switched off):
@@ -1478,7 +1526,7 @@ void caddy_ctx::prepare_inference_weights() {
     }
     pack_all(use_fold);
 }
-static int start_inference(caddy_ctx* c) {
+static int start_inference(caddy_ctx* c, int n) {
     bool dry = c->dry;
     c->training = false; c->recording = false;
     if (c->graph_exec && !dry) { hipStreamSynchronize(c->stream); if (c->gstream) hipStreamSynchronize(c->gstream); }  // a graph launch of the previous roll-out may still be executing: never destroy its exec object under it
@@ -1486,11 +1534,12 @@ static int start_inference(caddy_ctx* c) {
     c->prepare_inference_weights();
     for (int i = 0; i < 3; i++) {
         LstmL& L = c->lstm[i];
-        T4 ih = L.ih, ic = L.ic; ih.sn = 0; ic.sn = 0; ih.N = 1; ic.N = 1;
-        T4 ph = L.ph, pc = L.pc; ph.N = 1; pc.N = 1;
+        T4 ih = L.ih, ic = L.ic; ih.sn = 0; ic.sn = 0; ih.N = n; ic.N = n;      // the learned initial state, repeated over the sequence slots 0 .. n - 1
+        T4 ph = L.ph, pc = L.pc; ph.N = n; pc.N = n;
         if (!dry) { c->ck(pw_copy(dv(ih), dv(ph), 0, c->stream), "init h"); c->ck(pw_copy(dv(ic), dv(pc), 0, c->stream), "init c"); }
-        L.h = L.ph; L.c = L.pc; L.h.N = 1; L.c.N = 1;
+        L.h = L.ph; L.c = L.pc; L.h.N = n; L.c.N = n;
     }
+    c->roll_n = n;
     return c->fail ? -1 : 0;
 }
 
@@ -1747,7 +1796,17 @@ int caddy_set_precision(caddy_ctx* c, int forward, int backward) {
 }
 int caddy_start_inference(caddy_ctx* c) {
     if (!ctx_needs(c, CTX_MODEL, "caddy_start_inference")) return -2;
-    c->fail = false; return start_inference(c);
+    c->fail = false; return start_inference(c, 1);
+}
+int caddy_start_inference_batch(caddy_ctx* c, int n) {
+    if (!ctx_needs(c, CTX_MODEL, "caddy_start_inference_batch")) return -2;
+    if (n < 1 || n > c->cfg.batch) { set_error("caddy_start_inference_batch: n = " + std::to_string(n) + " is outside [1, caddy_config.batch = " + std::to_string(c->cfg.batch) + "]"); return -2; }
+    if (((long)c->cfg.height * c->cfg.width) & 3) {      // (the batched boundary kernels move four pixels of a plane per access)
+        set_error("caddy_start_inference_batch: height x width = " + std::to_string(c->cfg.height) + " x " + std::to_string(c->cfg.width) + " is not a multiple of 4 pixels"); return -2; }
+    for (int i = 0; i < 3; i++)      // (and the state reset copies float4s: roll_state)
+        if ((c->lstm[i].ph.sn & 3) || (c->lstm[i].pc.sn & 3)) { set_error("caddy_start_inference_batch: the ConvLSTM state of a sequence is not a multiple of 4 floats"); return -2; }
+    if (n > ROLL_CTL_MAX) { set_error("caddy_start_inference_batch: n = " + std::to_string(n) + " exceeds the " + std::to_string(ROLL_CTL_MAX) + " sequences one boundary launch carries"); return -2; }
+    c->fail = false; return start_inference(c, n);
 }
 // Poll of the per-layer f16 range guards: waits for the stream, reads and clears the flag words.  Returns bit 0: a split-f16 forward convolution (model or VGG19) staged |x| > 65504
 // since the last poll (it was clamped); bit 1: a NaN was among them.  The layers that reported -- and only those -- run without a range limit from the next forward on (exact fp32 /
@@ -1778,8 +1837,48 @@ int caddy_generate_next(caddy_ctx* c, const float* observation, int action, cons
         if ((obs_out && overlap(observation, ob, obs_out, ob)) || overlap(observation, ob, frame_out, fb) || (obs_out && overlap(obs_out, ob, frame_out, fb))) {
             set_error("caddy_generate_next: observation, frame_out and obs_out must not overlap (in-place update of the stacked observation is not supported)"); return -2; }
     }
-    if (c->lstm[0].h.d != c->lstm[0].ph.d || c->lstm[0].h.d == nullptr) { set_error("call caddy_start_inference first"); return -2; }
+    if (c->lstm[0].h.d != c->lstm[0].ph.d || c->lstm[0].h.d == nullptr || c->roll_n < 1) { set_error("call caddy_start_inference first"); return -2; }
+    if (c->roll_n != 1) { set_error("caddy_generate_next: the roll-out was started for " + std::to_string(c->roll_n) + " sequences (caddy_start_inference_batch): use caddy_generate_next_batch"); return -2; }
     return generate_next(c, observation, action, variation, frame_out, obs_out);
+}
+// true + caddy_last_error unless a roll-out of n >= 1 sequences is under way (caddy_start_inference[_batch] since the last forward pass)
+static bool rollout_not_started(caddy_ctx* c, const char* who) {
+    if (c->lstm[0].h.d == c->lstm[0].ph.d && c->lstm[0].h.d != nullptr && c->roll_n >= 1) return false;
+    set_error(std::string(who) + ": call caddy_start_inference_batch first"); return true;
+}
+int caddy_generate_next_batch(caddy_ctx* c, const float* observations, const int* actions, const float* variations, const unsigned char* reset, float* frames_out, float* obs_out) {
+    if (!ctx_needs(c, CTX_MODEL, "caddy_generate_next_batch")) return -2;
+    c->fail = false;
+    if (!observations || !actions || !frames_out) { set_error("null input"); return -2; }
+    if (rollout_not_started(c, "caddy_generate_next_batch")) return -2;
+    const int n = c->roll_n;
+    for (int s = 0; s < n; s++)
+        if (actions[s] < 0 || actions[s] >= c->cfg.actions) { set_error("caddy_generate_next_batch: action " + std::to_string(actions[s]) + " of sequence " + std::to_string(s) + " out of range [0, " + std::to_string(c->cfg.actions) + ")"); return -2; }
+    {   // as caddy_generate_next: the boundary kernel behind the frame reads `observations` while it writes obs_out and frames_out
+        const size_t ob = sizeof(float) * 3 * (size_t)c->cfg.stacking * c->cfg.height * c->cfg.width * n, fb = sizeof(float) * 3 * (size_t)c->cfg.height * c->cfg.width * n;
+        auto overlap = [](const void* a, size_t na, const void* b, size_t nb) { return (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na; };
+        if ((obs_out && overlap(observations, ob, obs_out, ob)) || overlap(observations, ob, frames_out, fb) || (obs_out && overlap(obs_out, ob, frames_out, fb))) {
+            set_error("caddy_generate_next_batch: observations, frames_out and obs_out must not overlap (in-place update of the stacked observations is not supported)"); return -2; }
+        if ((((uintptr_t)observations | (uintptr_t)frames_out | (uintptr_t)obs_out) & 15) || (variations && ((uintptr_t)variations & 3))) {
+            set_error("caddy_generate_next_batch: observations, frames_out and obs_out must be 16-byte aligned (the boundary kernels move 16 bytes per access)"); return -2; }
+    }
+    return generate_next_batch(c, observations, actions, variations, reset, frames_out, obs_out);
+}
+int caddy_rollout_copy_state(caddy_ctx* c, int src, int dst) {
+    if (!ctx_needs(c, CTX_MODEL, "caddy_rollout_copy_state")) return -2;
+    c->fail = false;
+    if (rollout_not_started(c, "caddy_rollout_copy_state")) return -2;
+    if (src < 0 || src >= c->roll_n || dst < 0 || dst >= c->roll_n) {
+        set_error("caddy_rollout_copy_state: slots (" + std::to_string(src) + ", " + std::to_string(dst) + ") outside [0, n = " + std::to_string(c->roll_n) + ")"); return -2; }
+    if (src == dst) return 0;
+    for (int i = 0; i < 3 && !c->dry; i++) {
+        LstmL& L = c->lstm[i];
+        for (const T4* t : {&L.ph, &L.pc}) {
+            T4 a = *t, b = *t; a.N = b.N = 1; a.d += (long)src * t->sn; b.d += (long)dst * t->sn;
+            c->ck(pw_copy(dv(a), dv(b), 0, c->stream), "roll-out state copy");
+        }
+    }
+    return c->fail ? -1 : 0;
 }
 int caddy_profile_begin(caddy_ctx* c) { c->prof = true; c->prof_recs.clear(); c->phases.clear(); c->ev_used = 0; return 0; }
 // phase marks of the profiled steps: names_out receives `max` x 48-byte names, ms_out the time since the previous mark on the main stream; returns the count
@@ -1823,6 +1922,7 @@ int caddy_profile_end(caddy_ctx* c, double* out18) {   // CK_COUNT kernel famili
 }
 int caddy_debug_fusion_counts(caddy_ctx* c, long* out3) { out3[0] = c->n_bn_calls; out3[1] = c->n_bn_tile_stats; out3[2] = c->n_bn_lazy; return 0; }
 int caddy_debug_count(caddy_ctx* c) { return (int)c->dbg.size(); }
+int caddy_debug_rollout_graph_nodes(caddy_ctx* c) { return c->graph_valid ? c->graph_kernels : 0; }
 int caddy_debug_dims(caddy_ctx* c, int i, int* nhwc4) {
     if (i < 0 || i >= (int)c->dbg.size()) return -1;
     nhwc4[0] = c->dbg[i].N; nhwc4[1] = c->dbg[i].H; nhwc4[2] = c->dbg[i].W; nhwc4[3] = c->dbg[i].C; return 0;

@@ -235,6 +235,8 @@ struct caddy_ctx {
     T4 roll_frame{};                 // full-resolution frame (NHWC, pitch 4) of the per-frame kernel sequence
     hipStream_t gstream = nullptr; hipGraph_t graph = nullptr; hipGraphExec_t graph_exec = nullptr;
     bool graph_valid = false, graph_failed = false, use_graph = true;
+    int roll_n = 0;                  // sequences of the roll-out under way (caddy_start_inference: 1, caddy_start_inference_batch: n <= cfg.batch); 0: none started
+    int graph_n = 0, graph_kernels = 0;      // batch extent the captured graph was recorded for; its kernel nodes (-1: not counted)
     hipEvent_t gev_in = nullptr, gev_out = nullptr;
     void drop_graph();
     // BatchNorm folding for the roll-out (weights are constant between start_inference calls): `fold` switches encode / dynamics / render to the

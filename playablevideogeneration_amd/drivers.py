@@ -211,10 +211,32 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
     return {"frames": np.stack(frames, axis=0), **meta}
 
 
-def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, second_action: int, steps: int, frames_count: int, out_dir: Optional[str] = None) -> List[np.ndarray]:
-    """interpolate.py:102-158: for each value in linspace(0, 1, steps + 1) one sequence of `frames_count` generate_next_interpolation calls from the same start"""
+def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, second_action: int, steps: int, frames_count: int, out_dir: Optional[str] = None,
+                     batched: bool = False) -> List[np.ndarray]:
+    """interpolate.py:102-158: for each value in linspace(0, 1, steps + 1) one sequence of `frames_count` generate_next_interpolation calls from the same start.
+    batched: all steps + 1 sequences advance as one batch per frame (one graph launch instead of steps + 1)."""
     model.eval()
     sequences = []
+    if batched:
+        alphas = np.linspace(0.0, 1.0, steps + 1).tolist()
+        n = len(alphas)
+        with torch.no_grad():
+            model.start_inference(batch_size=n)
+            obs = torch.stack([start_observation] * n)
+            frame = obs[:, :3]
+            frames = []
+            for i in range(frames_count + 1):
+                imgs = [frame_to_uint8(frame[si]) for si in range(n)]
+                frames.append(imgs)
+                if out_dir is not None:
+                    from PIL import Image
+                    for si in range(n):
+                        os.makedirs(os.path.join(out_dir, str(si)), exist_ok=True)
+                        Image.fromarray(imgs[si]).save(os.path.join(out_dir, str(si), f"{i}.png"))
+                if i == frames_count:
+                    break
+                frame, obs = model.generate_next_interpolation_batch(obs, first_action, second_action, alphas)
+        return [np.stack([f[si] for f in frames], axis=0) for si in range(n)]
     with torch.no_grad():
         for si, alpha in enumerate(np.linspace(0.0, 1.0, steps + 1).tolist()):
             model.start_inference()
@@ -309,6 +331,7 @@ def main(argv=None) -> int:
     p.add_argument("--out", default="play_results"); p.add_argument("--sample", default="0:0", help="batch_index:observation_index of the first validation batch")
     p = sub.add_parser("interpolate"); p.add_argument("--config", required=True); p.add_argument("--first", type=int, required=True); p.add_argument("--second", type=int, required=True)
     p.add_argument("--steps", type=int, default=6); p.add_argument("--frames", type=int, default=8); p.add_argument("--out", default=None)
+    p.add_argument("--batched", action="store_true", help="advance all steps + 1 sequences as one batch per frame")
     p = sub.add_parser("build-dataset"); p.add_argument("--config", required=True)
     p = sub.add_parser("evaluate"); p.add_argument("--config", required=True)
     args = ap.parse_args(argv)
@@ -336,7 +359,7 @@ def main(argv=None) -> int:
         logger.print(f"- {len(res['frames'])} frames written to {os.path.join(args.out, '0')}")
         return 0
     out = args.out or config["logging"]["interpolated_sequences"]
-    interpolate_loop(model, obs[0, 0].cuda(), args.first, args.second, args.steps, args.frames, out)
+    interpolate_loop(model, obs[0, 0].cuda(), args.first, args.second, args.steps, args.frames, out, batched=args.batched)
     logger.print(f"- {args.steps + 1} sequences written to {out}")
     return 0
 

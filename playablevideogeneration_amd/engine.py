@@ -115,6 +115,9 @@ def _bind(lib):
     lib.caddy_sequence_losses_per_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.caddy_set_deterministic.argtypes = [C.c_void_p, C.c_int]
     lib.caddy_generate_next.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.caddy_start_inference_batch.argtypes = [C.c_void_p, C.c_int]
+    lib.caddy_generate_next_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_ubyte), C.c_void_p, C.c_void_p]
+    lib.caddy_rollout_copy_state.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.caddy_bn_layer_count.argtypes = [C.c_void_p]
     lib.caddy_bn_calls.argtypes = [C.c_void_p, C.c_int, C.c_char_p]
     lib.caddy_bn_calls.restype = C.c_long
@@ -551,9 +554,12 @@ class Engine:
         """convolution layers this engine has moved off the split-f16 forward after a range-guard report"""
         return int(self.lib.caddy_fallback_layers(self.ctx))
 
-    def start_inference(self):
+    def start_inference(self, n: int = 1):
+        """(re)start a roll-out of `n` independent sequences (1 <= n <= batch): their ConvLSTM memories are re-initialised.  n = 1 is the play.py path (generate_next);
+        any n is advanced by generate_next_batch."""
         self._stream()
-        self._check(self.lib.caddy_start_inference(self.ctx))
+        self._check(self.lib.caddy_start_inference(self.ctx) if n == 1 else self.lib.caddy_start_inference_batch(self.ctx, int(n)))
+        self._roll_n = int(n)
 
     def generate_next(self, observation: torch.Tensor, action: int, variation: Optional[torch.Tensor] = None):
         S, H, W = self.S, self.H, self.W
@@ -566,6 +572,38 @@ class Engine:
         self._check(self.lib.caddy_generate_next(self.ctx, obs.data_ptr(), int(action), v.data_ptr() if v is not None else None,
                                                  frame.data_ptr(), nxt.data_ptr()))
         return frame, nxt
+
+    def generate_next_batch(self, observations: torch.Tensor, actions, variations: Optional[torch.Tensor] = None, reset=None):
+        """One step of every sequence of the roll-out started by start_inference(n): observations (n, 3S, H, W), actions n ints, variations (n, Da) or None (zeros),
+        reset n flags or None (a set flag re-initialises that sequence's memory before the step).  Returns (frames (n, 3, H, W), next_observations (n, 3S, H, W))."""
+        S, H, W = self.S, self.H, self.W
+        n = getattr(self, "_roll_n", 0)
+        if n < 1:
+            raise CaddyError("generate_next_batch: call start_inference(n) first")
+        obs = observations.to(self.device, torch.float32).contiguous()
+        acts = [int(a) for a in (actions.tolist() if isinstance(actions, torch.Tensor) else actions)]
+        if tuple(obs.shape) != (n, 3 * S, H, W) or len(acts) != n:
+            raise CaddyError(f"generate_next_batch: the roll-out holds {n} sequences of shape {(3 * S, H, W)}: got observations {tuple(obs.shape)} and {len(acts)} actions")
+        frames = torch.empty((n, 3, H, W), dtype=torch.float32, device=self.device)
+        nxt = torch.empty((n, 3 * S, H, W), dtype=torch.float32, device=self.device)
+        v = None
+        if variations is not None:
+            v = variations.to(self.device, torch.float32).contiguous()
+            assert tuple(v.shape) == (n, self.Da)
+        r = None
+        if reset is not None:
+            flags = [1 if f else 0 for f in (reset.tolist() if isinstance(reset, torch.Tensor) else reset)]
+            assert len(flags) == n
+            r = (C.c_ubyte * n)(*flags)
+        self._stream()
+        self._check(self.lib.caddy_generate_next_batch(self.ctx, obs.data_ptr(), (C.c_int * n)(*acts), v.data_ptr() if v is not None else None, r,
+                                                       frames.data_ptr(), nxt.data_ptr()))
+        return frames, nxt
+
+    def copy_rollout_state(self, src: int, dst: int):
+        """fork: the ConvLSTM memory of sequence slot `src` into slot `dst` (both then continue independently)"""
+        self._stream()
+        self._check(self.lib.caddy_rollout_copy_state(self.ctx, int(src), int(dst)))
 
     CONV_FAMILIES = ["k_conv_fwd<2, 2, 2, 2, 0, 1>", "k_conv_fwd<2, 1, 2, 2, 0, 1>", "k_conv_fwd<1, 1, 2, 2, 0, 1>", "k_conv_fwd<1, 1, 4, 1, 0, 1>",
                      "k_conv_thin_out", "k_conv_thin_in", "k_conv_wgrad<2, 2, 2, 2>", "k_conv_wgrad<1, 2, 2, 2>", "k_conv_wgrad<1, 1, 1, 4>",

@@ -87,6 +87,8 @@ class Model(nn.Module):
         self._engines: Dict[Tuple[int, int], Engine] = {}
         self._vgg_state = None           # VGG19 weights of the perceptual loss (set by the trainer: enable_perceptual)
         self._infer: Optional[Engine] = None
+        self._infer_batch: Dict[int, Engine] = {}      # batched roll-out: one inference engine per batch size > 1
+        self._infer_n = 0                # sequences of the roll-out under way (start_inference)
         self._bn_seen: Dict[Tuple[int, int], Dict[str, int]] = {}
         self.last_engine: Optional[Engine] = None
         self.centroid_estimator_view = _CentroidView(self)
@@ -177,6 +179,8 @@ class Model(nn.Module):
         self._rebind()
         self._engines.clear()
         self._infer = None
+        self._infer_batch.clear()
+        self._infer_n = 0
         return self
 
     def zero_grad(self, set_to_none: bool = False):
@@ -303,15 +307,31 @@ class Model(nn.Module):
                           "layer(s) now run without a range limit -- repeat the pass for unclamped results")
 
     # ---- play.py path (model.py:561-607) ---------------------------------------------------------------------------------
-    def start_inference(self):
+    def start_inference(self, batch_size: int = 1):
+        """model.py:561-568; batch_size > 1 starts that many independent sequences, advanced together by generate_next_batch (one inference engine is kept per batch size)"""
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise Exception("start_inference(): batch_size must be >= 1")
+        if batch_size > 1:
+            if batch_size not in self._infer_batch:
+                self._infer_batch[batch_size] = Engine(batch=batch_size, seq_len=2, device=self._flat.device, lib=self._lib, params=self._flat, grads=self._flat_grad, **self.dims)
+            self._infer_batch[batch_size].start_inference(batch_size)
+            self._infer_n = batch_size
+            return
         if self._infer is None:
             d = self.dims
             self._infer = Engine(batch=1, seq_len=2, device=self._flat.device, lib=self._lib, params=self._flat, grads=self._flat_grad, **d)
         self._infer.start_inference()
+        self._infer_n = 1
+
+    def _single_rollout(self, who: str):
+        if self._infer_n != 1:      # (the single-sequence engine would go on from an earlier roll-out's ConvLSTM state)
+            raise Exception(f"{who}(): the roll-out under way was started with start_inference(batch_size={self._infer_n}): use {who}_batch(), or call start_inference() first")
 
     def generate_next(self, observation: torch.Tensor, action: int, noise=False):
         if self._infer is None:
             raise Exception("start_inference() must be called before generate_next()")
+        self._single_rollout("generate_next")
         variation = torch.randn((1, self.dims["action_dim"]), dtype=torch.float32)[0] if noise else None
         torch.randn((1, self.random_noise_size))             # generate_noise(batch_size=1), unused by R (model.py:596)
         out = self._infer.generate_next(observation, action, variation)
@@ -325,11 +345,59 @@ class Model(nn.Module):
         """model.py:609-655: act with the centroid nearer to the interpolated point, the offset to it as the action variation."""
         if self._infer is None:
             raise Exception("start_inference() must be called before generate_next_interpolation()")
+        self._single_rollout("generate_next_interpolation")
         cen = self.centroid_estimator.get_estimated_centroids()
         selected = second_action if interpolation_factor > 0.5 else first_action
         point = (cen[second_action] - cen[first_action]) * interpolation_factor + cen[first_action]
         torch.randn((1, self.random_noise_size))             # generate_noise(batch_size=1), unused by R
         return self._infer.generate_next(observation, selected, (point - cen[selected]).detach())
+
+
+    # ---- the same for a batch of independent sequences: every sequence advances as one reference call would advance it ----
+    def _batch_engine(self, n: int) -> Engine:
+        if self._infer_n < 1 or n != self._infer_n:
+            raise Exception(f"start_inference(batch_size={n}) must be called before a batched step of {n} sequences")
+        return self._infer if n == 1 else self._infer_batch[n]
+
+    def _batch_step(self, eng: Engine, observations, actions, variations, reset=None):
+        out = eng.generate_next_batch(observations, actions, variations, reset)
+        self._frames_since_poll = getattr(self, "_frames_since_poll", 0) + 1
+        if self._frames_since_poll >= 64:                    # (a poll waits for the stream: every 64th call, as generate_next)
+            self._frames_since_poll = 0
+            self._check_numerics(eng)
+        return out
+
+    def generate_next_batch(self, observations: torch.Tensor, actions, noise=False, reset=None):
+        """generate_next for n sequences at once: observations (n, 3S, H, W), actions n ints -> (frames (n, 3, H, W), next observations (n, 3S, H, W)).
+        The torch RNG is consumed as n reference calls would consume it, sequence by sequence: one randn(1, Da) when `noise`, one randn(1, random_noise_size)."""
+        n = int(observations.shape[0])
+        eng = self._batch_engine(n)
+        rows = []
+        for _ in range(n):
+            if noise:
+                rows.append(torch.randn((1, self.dims["action_dim"]), dtype=torch.float32)[0])
+            torch.randn((1, self.random_noise_size))         # generate_noise(batch_size=1), unused by R (model.py:596)
+        return self._batch_step(eng, observations, actions, torch.stack(rows) if noise else None, reset)
+
+    def generate_next_interpolation_batch(self, observations: torch.Tensor, first_actions, second_actions, factors):
+        """generate_next_interpolation for n sequences at once (model.py:609-655 per sequence); first_actions / second_actions / factors: n values each (a scalar is repeated)"""
+        n = int(observations.shape[0])
+        eng = self._batch_engine(n)
+
+        def per_seq(v):
+            v = v.tolist() if hasattr(v, "tolist") else v
+            return list(v) if isinstance(v, (list, tuple)) else [v] * n
+        first, second, factors = per_seq(first_actions), per_seq(second_actions), per_seq(factors)
+        assert len(first) == n and len(second) == n and len(factors) == n
+        cen = self.centroid_estimator.get_estimated_centroids()
+        selected, rows = [], []
+        for a1, a2, al in zip(first, second, factors):
+            sel = a2 if al > 0.5 else a1
+            point = (cen[a2] - cen[a1]) * al + cen[a1]
+            torch.randn((1, self.random_noise_size))         # generate_noise(batch_size=1), unused by R
+            selected.append(int(sel))
+            rows.append((point - cen[sel]).detach())
+        return self._batch_step(eng, observations, selected, torch.stack(rows))
 
 
 def model(config):
