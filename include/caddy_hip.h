@@ -254,6 +254,30 @@ int caddy_debug_fvd_fallback_layers(caddy_ctx* ctx);
 /* measurement: on != 0 records events at the stage boundaries of the following chunks; ms5 (nullable) receives the times of the last chunk's input stage (fvd.py:49-56), stem,
  * Mixed_3, Mixed_4 and Mixed_5 + head */
 int caddy_debug_fvd_stage_ms(caddy_ctx* ctx, int on, float* ms5);
+/* --- Device-side frame pipeline (csrc/frames.hip): the distinct decoded uint8 RGB frames of one batch in, the model's observation tensor out.  Replaces, on the device, the
+ *     host's per-frame crop -> bilinear resize -> normalise (dataset/transforms.py:13-30,90-107) and the channel-concatenating / stacking collate (dataset/batching.py:97-112).
+ *     The arithmetic is PIL's 8-bit Image.crop(box) + Image.resize(size, BILINEAR), bit for bit: per axis the triangle filter of support max(in / out, 1), its weights
+ *     normalised in double and quantised to 22 fractional bits, out = clip8((2^21 + sum pixel * kk) >> 22), horizontal pass first with a uint8 intermediate, a pass skipped
+ *     when its axis keeps its size; the tables are built once on the host at creation.  A FRAMES context is an evaluation context of its own kind (no model, no weights):
+ *     source frames of src_h x src_w, crop4 = {left, upper, right, lower} or NULL for the whole frame, output frames of out_h x out_w, at most max_frames source frames per call.
+ *     lut512 (host memory): 2 x 256 floats, the value of every byte under mode 0 (((x / 255) - 0.5) / 0.5, transforms.py:99-102) and mode 1 (x / 255, transforms.py:67-87),
+ *     computed by the caller with the host's own expression so that the result equals the host path's by construction.  caddy_frames_workspace_bytes returns 0
+ *     (caddy_last_error) for a crop box that is not inside the source frame (PIL would pad with black) or a geometry whose single output row does not fit the kernel's LDS.
+ *     Destroy with caddy_ctx_destroy. --- */
+size_t caddy_frames_workspace_bytes(int max_frames, int src_h, int src_w, const int* crop4, int out_h, int out_w);                                       /* dataset/transforms.py:13-30 */
+caddy_ctx* caddy_frames_ctx_create(int max_frames, int src_h, int src_w, const int* crop4, int out_h, int out_w, const float* lut512, void* workspace, size_t bytes);   /* dataset/transforms.py:90-107 */
+/* tests: the host copies of the filter tables of axis 0 (horizontal) / 1 (vertical): *ksize taps per output, bounds = out x (first source index, tap count), kk = out x ksize
+ * quantised weights (each nullable).  Returns 1 when the kernel runs that pass, 0 when the axis keeps its size and the pass is skipped, -2 on error. */
+int caddy_frames_tables_get(caddy_ctx* ctx, int axis, int* ksize, int* bounds, int* kk);                                                                 /* dataset/transforms.py:13-30 */
+/* tests: plan5 receives the output rows per workgroup, the most source rows one workgroup keeps, the source rows staged per round of the horizontal pass, the LDS bytes
+ * used and the LDS bytes of the kernel variant chosen */
+int caddy_debug_frames_plan(caddy_ctx* ctx, int* plan5);
+/* frames = (n_frames, src_h, src_w, 3) uint8 on the device, 4-byte aligned; slot_src = n_slots int32 on the device; out = (n_slots, 3, out_h, out_w) planar fp32 on the device:
+ * plane triple i is frame slot_src[i] cropped, resized and mapped through the table of `mode`.  Viewed as (bs, T, 3 S, out_h, out_w), slot i is (b, t, s) in row-major order,
+ * newest frame first (dataset/video_dataset.py:131-137, dataset/batching.py:97-112).  A slot whose source lies outside [0, n_frames) reads nothing and is filled with NaN.
+ * One launch on the context's stream; waits for nothing, allocates nothing, deterministic.  Errors (-2, caddy_last_error): a context of another kind, null or misaligned
+ * pointers, n_frames > max_frames, n_frames or n_slots < 1, mode other than 0 or 1. */
+int caddy_frames_to_observations(caddy_ctx* ctx, const unsigned char* frames, int n_frames, const int* slot_src, int n_slots, int mode, float* out);    /* dataset/batching.py:97-112 */
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

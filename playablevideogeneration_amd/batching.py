@@ -4,6 +4,8 @@
     BatchElement/Batch  dataset/batching.py:10-95          (`to_tuple()` -> (observations, actions, rewards, dones), `.size`)
     collate             dataset/batching.py:97-112         (stack of per-observation channel-concatenated frame stacks)
     normalisation       dataset/transforms.py:90-107       (ToTensor + Normalize(0.5, 0.5): uint8 [0, 255] -> fp32 [-1, 1])
+    device transforms   (opt-in) RawBatchElement / RawBatch: the distinct uint8 frames of a batch plus the (bs, T, S) list of which frame fills which
+                        slot; `RawBatch.to_tuple()` runs crop, resize, normalisation and stacking as one HIP kernel (frame_pipeline.py, csrc/frames.hip)
 
 The tensor contract lives here; the reader of the reference's on-disk format (PNG folders + pickles, dataset/video.py) and the sample
 grid over videos is `playablevideogeneration_amd.video_dataset`.  `Batch.to_tuple()` moves
@@ -88,6 +90,80 @@ def single_batch_elements_collate_fn(batch: List[BatchElement]) -> Batch:
     rewards = torch.stack([torch.tensor(el.rewards) for el in batch], dim=0)
     dones = torch.stack([torch.tensor(el.dones) for el in batch], dim=0)
     return Batch(obs, actions, rewards, dones, [el.video for el in batch], [el.initial_frame_index for el in batch])
+
+
+class RawBatchElement:
+    """One sampled sequence before any transform (video_dataset.raw_frame_spec): `frames` are its distinct decoded frames, (h, w, 3) uint8 arrays, `stack_indices[i][s]`
+    the index into them of stack position s (newest first) of observation i; annotations as in BatchElement."""
+
+    def __init__(self, frames, stack_indices, actions, rewards, dones, spec, video=None, initial_frame_index: int = 0):
+        self.observations_count = len(stack_indices)
+        self.observations_stacking = len(stack_indices[0])
+        if len(actions) != self.observations_count or len(rewards) != self.observations_count or len(dones) != self.observations_count:
+            raise Exception("Missing elements in the current batch")
+        self.frames, self.stack_indices, self.spec = frames, stack_indices, spec
+        self.actions, self.rewards, self.dones = actions, rewards, dones
+        self.video, self.initial_frame_index = video, initial_frame_index
+
+
+class RawBatch:
+    """`frames` (F, h, w, 3) uint8, `slot_src` (bs, T, S) int32 indices into them, (bs, T) actions / rewards / dones: what the host ships when the frame
+    transform runs on the device.  `to_tuple()` returns what `Batch.to_tuple()` returns, bit for bit."""
+
+    def __init__(self, frames: torch.Tensor, slot_src: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor, dones: torch.Tensor, spec, videos=None, initial_frames=None):
+        self.size = actions.size(1)
+        self.frames, self.slot_src, self.spec = frames, slot_src, spec
+        self.actions, self.rewards, self.dones = actions, rewards, dones
+        self.video, self.initial_frames = videos, initial_frames
+
+    def observations(self, frames: torch.Tensor = None, slot_src: torch.Tensor = None, lib=None, device=None) -> torch.Tensor:
+        """(bs, T, 3 S, H, W) fp32 on the pipeline's device, from this batch's frames (or their staged copies) on the current stream"""
+        from .frame_pipeline import cached_pipeline, validate_slots
+        validate_slots(self.slot_src, int(self.frames.shape[0]))
+        frames = self.frames if frames is None else frames
+        slot_src = self.slot_src if slot_src is None else slot_src
+        pipe = cached_pipeline(int(self.frames.shape[1]), int(self.frames.shape[2]), self.spec.crop, self.spec.size, self.spec.mode, int(self.frames.shape[0]), lib, device)
+        bs, T, S = self.slot_src.shape
+        return pipe(frames, slot_src).view(bs, T, 3 * S, pipe.H, pipe.W)
+
+    def to_tuple(self, cuda=True) -> Tuple:
+        obs = self.observations()
+        rest = (self.actions, self.rewards, self.dones)
+        if not cuda:
+            return (obs.cpu(),) + rest
+        if torch.cuda.is_available():
+            rest = tuple(t.cuda(non_blocking=True) for t in rest)
+        return (obs,) + rest
+
+    def pin_memory(self):
+        self.frames, self.slot_src = self.frames.pin_memory(), self.slot_src.pin_memory()
+        self.actions, self.rewards, self.dones = self.actions.pin_memory(), self.rewards.pin_memory(), self.dones.pin_memory()
+        return self
+
+
+def raw_batch_elements_collate_fn(batch: List[RawBatchElement]) -> RawBatch:
+    """the collate function of RawBatchElements: frames are concatenated once each, the stack indices shifted by the frames in front of their element"""
+    import numpy as np
+    shape = batch[0].frames[0].shape
+    frames, slots = [], []
+    for el in batch:
+        for fr in el.frames:
+            if fr.shape != shape:
+                raise Exception(f"frames of different sizes in one batch: {tuple(shape)} and {tuple(fr.shape)} (such datasets keep the host transform)")
+        slots.append(torch.tensor(el.stack_indices, dtype=torch.int32) + len(frames))
+        frames.extend(el.frames)
+    actions = torch.stack([torch.tensor(el.actions, dtype=torch.int) for el in batch], dim=0)
+    rewards = torch.stack([torch.tensor(el.rewards) for el in batch], dim=0)
+    dones = torch.stack([torch.tensor(el.dones) for el in batch], dim=0)
+    return RawBatch(torch.from_numpy(np.stack(frames)), torch.stack(slots, dim=0), actions, rewards, dones, batch[0].spec,
+                    [el.video for el in batch], [el.initial_frame_index for el in batch])
+
+
+def collate_fn_for(element):
+    """the collate function of a dataset whose items look like `element`: raw elements, BatchElements, or None for anything else"""
+    if isinstance(element, RawBatchElement):
+        return raw_batch_elements_collate_fn
+    return single_batch_elements_collate_fn if is_batch_element(element) else None
 
 
 def multiple_batch_elements_collate_fn(batch: List[Tuple[BatchElement]]) -> List[Batch]:

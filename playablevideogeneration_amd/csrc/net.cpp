@@ -6,6 +6,7 @@
 #include "net.h"
 #include "fid.h"
 #include "fvd.h"
+#include "frames.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1678,6 +1679,7 @@ void caddy_ctx_destroy(caddy_ctx* c) {
     if (c && c->dstream) { hipStreamSynchronize(c->dstream); hipStreamDestroy(c->dstream); if (c->d_done) hipEventDestroy(c->d_done); }
     fid_free(c);
     fvd_free(c);
+    frames_free(c);
     delete c;
 }
 int caddy_set_stream(caddy_ctx* c, void* s) { c->stream = (hipStream_t)s; return 0; }

@@ -32,14 +32,17 @@ class DatasetEvaluator:
 
     def __init__(self, config, logger, reference_dataset, generated_dataset):
         from torch.utils.data import DataLoader
-        from .batching import single_batch_elements_collate_fn
+        from .batching import collate_fn_for, single_batch_elements_collate_fn
         from .trainer import Trainer
         self.config, self.logger = config, logger
         self.reference_dataset, self.generated_dataset = reference_dataset, generated_dataset
         b = config["evaluation"]["batching"]
-        self.reference_dataloader = DataLoader(reference_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=single_batch_elements_collate_fn,
+
+        def collate(ds):      # raw elements (evaluation.device_transforms) bring their own collate function
+            return (collate_fn_for(ds[0]) if len(ds) else None) or single_batch_elements_collate_fn
+        self.reference_dataloader = DataLoader(reference_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=collate(reference_dataset),
                                                num_workers=b.get("num_workers", 0), pin_memory=torch.cuda.is_available())
-        self.generated_dataloader = DataLoader(generated_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=single_batch_elements_collate_fn,
+        self.generated_dataloader = DataLoader(generated_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=collate(generated_dataset),
                                                num_workers=b.get("num_workers", 0), pin_memory=torch.cuda.is_available())
         if len(self.reference_dataloader) != len(self.generated_dataloader):
             raise Exception(f"Reference and generated datasets should have the same sequences, but their length differs:"

@@ -166,8 +166,8 @@ def frame_to_uint8(frame: torch.Tensor) -> np.ndarray:
 def _first_observations(dataset, batch_size: int) -> torch.Tensor:
     """the first validation batch's observations (play.py:101-103, 118): (B, T, 3S, H, W)"""
     from torch.utils.data import DataLoader
-    from .batching import single_batch_elements_collate_fn
-    for batch in DataLoader(dataset, batch_size=batch_size, shuffle=False, collate_fn=single_batch_elements_collate_fn):
+    from .batching import collate_fn_for
+    for batch in DataLoader(dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_fn_for(dataset[0])):
         return batch.to_tuple(cuda=False)[0]
     raise Exception("the validation split is empty")
 
@@ -304,11 +304,15 @@ def load_evaluation_configuration(path: str, create_directories: bool = True) ->
 def evaluate_loop(config, logger) -> Dict:
     """evaluate_dataset.py:34-64 -> the metrics dict, also written to <output_directory>/data.yml"""
     import yaml
-    from .video_dataset import VideoDataset, evaluation_transform
+    from .video_dataset import VideoDataset, evaluation_transform, raw_frame_spec
     size = config["data"]["target_input_size"]
     logger.print("- Loading datasets")
-    reference = VideoDataset(config["reference_data"]["data_root"], config["evaluation"]["batching"], evaluation_transform(config["reference_data"].get("crop"), size))
-    generated = VideoDataset(config["generated_data"]["data_root"], config["evaluation"]["batching"], evaluation_transform(config["generated_data"].get("crop"), size))
+    if config["evaluation"].get("device_transforms", False):      # opt-in: crop, resize and x / 255 on the GPU (frame_pipeline.py)
+        def transform(crop): return raw_frame_spec(crop, size, 1)
+    else:
+        def transform(crop): return evaluation_transform(crop, size)
+    reference = VideoDataset(config["reference_data"]["data_root"], config["evaluation"]["batching"], transform(config["reference_data"].get("crop")))
+    generated = VideoDataset(config["generated_data"]["data_root"], config["evaluation"]["batching"], transform(config["generated_data"].get("crop")))
     logger.print("- Creating evaluator")
     path = config["evaluation"].get("evaluator", DEFAULT_DATASET_EVALUATOR)
     if path.startswith("evaluation.dataset_evaluator"):      # the reference's own evaluator modules: this package's evaluator takes their place

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .action_samplers import OneHotActionSampler, ZeroActionVariationSampler
-from .batching import is_batch_element, single_batch_elements_collate_fn
+from .batching import collate_fn_for
 
 
 class EvaluationVideo:
@@ -54,10 +54,11 @@ class EvaluationDatasetBuilder:
         """DataLoader(dataset, batch_size, shuffle=False, collate_fn=single_batch_elements_collate_fn) for datasets of BatchElements
         (evaluation_dataset_builder.py:29); an iterable of ready batch tuples / Batch objects is used as it is."""
         ds = self.dataset
-        if hasattr(ds, "__getitem__") and hasattr(ds, "__len__") and len(ds) > 0 and is_batch_element(ds[0]):
+        collate = collate_fn_for(ds[0]) if hasattr(ds, "__getitem__") and hasattr(ds, "__len__") and len(ds) > 0 else None
+        if collate is not None:
             from torch.utils.data import DataLoader
             nw = int(self.config["evaluation"]["batching"].get("num_workers", 0))
-            return DataLoader(ds, batch_size=self.batch_size, shuffle=False, collate_fn=single_batch_elements_collate_fn, num_workers=nw)
+            return DataLoader(ds, batch_size=self.batch_size, shuffle=False, collate_fn=collate, num_workers=nw)
         return ds
 
     @staticmethod

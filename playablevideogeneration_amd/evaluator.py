@@ -75,9 +75,10 @@ class Evaluator:
         ds = self.dataset
         if hasattr(ds, "__getitem__") and hasattr(ds, "__len__") and not isinstance(ds, (list, tuple)) and len(ds) > 0:
             from torch.utils.data import DataLoader
-            from .batching import is_batch_element, single_batch_elements_collate_fn
-            if is_batch_element(ds[0]):                        # evaluation/evaluator.py:51: DataLoader(..., collate_fn=single_batch_elements_collate_fn)
-                return DataLoader(ds, batch_size=self.batch_size, shuffle=False, collate_fn=single_batch_elements_collate_fn)
+            from .batching import collate_fn_for
+            collate = collate_fn_for(ds[0])
+            if collate is not None:                            # evaluation/evaluator.py:51: DataLoader(..., collate_fn=single_batch_elements_collate_fn)
+                return DataLoader(ds, batch_size=self.batch_size, shuffle=False, collate_fn=collate)
             return DataLoader(ds, batch_size=self.batch_size, shuffle=False, collate_fn=getattr(ds, "collate_fn", None))
         return ds                                              # any iterable of Batch objects / batch tuples
 

@@ -5,6 +5,9 @@ the consumer's stream waits on -- the copy of batch i+1 overlaps the training st
 
     for batch_tuple in DevicePrefetcher(dataloader, device):          # yields (observations, actions, rewards, dones) on `device`
         trainer.compute_losses(model, batch_tuple, ...)
+
+A `batching.RawBatch` (device transforms) is staged as what it is -- the distinct uint8 frames and the int32 slot list, a quarter or less of the fp32 bytes -- and the
+frame pipeline's kernel runs on the prefetch stream behind the copies; the consumer sees the same tuple under the same event.
 """
 from typing import Iterable, Iterator, Optional, Tuple
 
@@ -32,7 +35,13 @@ class DevicePrefetcher:
         self._slot_event = [None, None]   # last copy issued from each slot's pinned buffers (host waits on it before overwriting them)
 
     def _stage(self, batch, slot):
-        items = _as_tuple(batch)
+        raw = batch if hasattr(batch, "slot_src") and hasattr(batch, "observations") else None
+        if raw is not None:      # frames and slots travel as they are; the observations are made on this stream, behind their copies
+            from .frame_pipeline import validate_slots
+            validate_slots(raw.slot_src, int(raw.frames.shape[0]))
+            items = (raw.frames, raw.slot_src, raw.actions, raw.rewards, raw.dones)
+        else:
+            items = _as_tuple(batch)
         out = []
         for i, t in enumerate(items):
             if not torch.is_tensor(t):
@@ -51,6 +60,8 @@ class DevicePrefetcher:
                 buf.copy_(t)
                 src = buf
             out.append(src.to(self.device, non_blocking=True))
+        if raw is not None:
+            out = [raw.observations(out[0], out[1], device=self.device if self.on_gpu else None)] + out[2:]
         return tuple(out)
 
     def __iter__(self) -> Iterator[Tuple]:

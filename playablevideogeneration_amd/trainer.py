@@ -89,14 +89,15 @@ class Trainer:
             return None
         b = config["training"]["batching"]
         try:
-            from .batching import single_batch_elements_collate_fn, is_batch_element
-            if len(dataset) == 0 or not is_batch_element(dataset[0]):
+            from .batching import collate_fn_for
+            collate = collate_fn_for(dataset[0]) if len(dataset) else None
+            if collate is None:
                 return None
         except Exception:
             return None
         from torch.utils.data import DataLoader
         nw = int(b.get("num_workers", 0))
-        return DataLoader(dataset, batch_size=b["batch_size"], shuffle=True, collate_fn=single_batch_elements_collate_fn, num_workers=nw,
+        return DataLoader(dataset, batch_size=b["batch_size"], shuffle=True, collate_fn=collate, num_workers=nw,
                           pin_memory=torch.cuda.is_available(), drop_last=True)
 
     # ---- schedules: training/trainer.py:124-165 ----

@@ -6,8 +6,11 @@
     frame transform  dataset/transforms.py:13-30,90-107  crop -> bilinear resize to `target_input_size` -> [0, 255] -> [-1, 1]
     splits           dataset/dataset_splitter.py:11-46   "flat" (fractions of one sorted directory) / "splitted" (train / val / test sub-directories)
 
-Nothing here touches the GPU: frames are decoded with PIL on the host (DataLoader workers), stacked by the collate function and moved by
-`Batch.to_tuple()` / `DevicePrefetcher`.  `EvaluationVideo.save` (evaluation_dataset_builder.py) writes the same format this module reads.
+By default frames are decoded and transformed with PIL on the host (DataLoader workers), stacked by the collate function and moved by `Batch.to_tuple()` /
+`DevicePrefetcher`.  With `raw_frame_spec(...)` in place of a transform (`data.device_transforms` / `evaluation.device_transforms`) the workers only decode: the
+dataset yields `RawBatchElement`s of distinct uint8 frames, and crop, resize, normalisation and stacking run on the GPU as one HIP kernel when the batch is turned
+into its tuple (batching.RawBatch, frame_pipeline.py, csrc/frames.hip) -- same bits, a quarter or less of the bytes.  `EvaluationVideo.save`
+(evaluation_dataset_builder.py) writes the same format this module reads.
 """
 import glob
 import os
@@ -18,7 +21,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from .batching import BatchElement, accumulated_rewards, available_samples, normalize_frame, observation_indices
+from .batching import BatchElement, RawBatchElement, accumulated_rewards, available_samples, normalize_frame, observation_indices
 
 ANNOTATION_FILES = ("actions", "rewards", "metadata", "dones")
 
@@ -105,6 +108,22 @@ def evaluation_transform(crop, target_input_size) -> Callable:
     return transform
 
 
+class RawFrameSpec:
+    """Marker a VideoDataset takes in place of a transform: its frames leave the dataset undecorated and `crop` ([left, upper, right, lower] or None), the resize to
+    `size` ((width, height)) and the normalisation of `mode` (0: final_transform's [-1, 1], 1: evaluation_transform's [0, 1]) run on the device."""
+
+    def __init__(self, crop, size, mode: int):
+        if mode not in (0, 1):
+            raise ValueError(f"mode must be 0 ([-1, 1]) or 1 ([0, 1]), got {mode}")
+        self.crop = None if crop is None else tuple(int(v) for v in crop)
+        self.size = tuple(int(v) for v in size)
+        self.mode = int(mode)
+
+
+def raw_frame_spec(crop, size, mode: int) -> RawFrameSpec:
+    return RawFrameSpec(crop, size, mode)
+
+
 class VideoDataset(Dataset):
     """Dataset of sampled sequences over a directory of videos (dataset/video_dataset.py:14-149).  `batching_config` is the reference's
     `training.batching` / `evaluation.batching` dict (observations_count, observation_stacking, skip_frames); `transform` maps a PIL frame to a
@@ -147,6 +166,8 @@ class VideoDataset(Dataset):
         vi, first = self.locate(index)
         video = self.all_videos[vi]
         obs_idx, stacks = observation_indices(first, self.observations_count, self.skip_frames, self.observations_stacking)
+        if isinstance(self.final_transform, RawFrameSpec):
+            return self._raw_element(video, first, obs_idx, stacks)
         cache: Dict[int, torch.Tensor] = {}
 
         def frame(i):                                         # consecutive stacks share frames: decode each once
@@ -156,6 +177,20 @@ class VideoDataset(Dataset):
         observations = [[frame(i) for i in st] for st in stacks]
         return BatchElement(observations, [video.actions[i] for i in obs_idx], accumulated_rewards(video.rewards, obs_idx, self.skip_frames),
                             [video.dones[i] for i in obs_idx], video, first)
+
+
+    def _raw_element(self, video, first, obs_idx, stacks) -> RawBatchElement:
+        """the sample's distinct frames, decoded once each and left as they are, plus where each goes"""
+        order = sorted({i for st in stacks for i in st})
+        where = {i: k for k, i in enumerate(order)}
+        frames = []
+        for i in order:
+            image = video.get_frame_at(i)
+            if image.mode != "RGB":      # PIL resizes palette and grey images differently: such datasets keep the host transform
+                raise Exception(f"{os.path.join(video.frames_path, f'{i:05d}.{video.extension}')}: PIL mode '{image.mode}', the device transforms take RGB frames only")
+            frames.append(np.asarray(image, dtype=np.uint8).copy())
+        return RawBatchElement(frames, [[where[i] for i in st] for st in stacks], [video.actions[i] for i in obs_idx],
+                               accumulated_rewards(video.rewards, obs_idx, self.skip_frames), [video.dones[i] for i in obs_idx], self.final_transform, video, first)
 
 
 def generate_splits(config) -> Dict[str, Tuple[str, Dict, Optional[List[str]]]]:
@@ -178,5 +213,8 @@ def generate_splits(config) -> Dict[str, Tuple[str, Dict, Optional[List[str]]]]:
 
 def build_datasets(config) -> Dict[str, VideoDataset]:
     """what train.py:42-51 does before it calls the trainer / evaluator factories"""
-    tf = final_transform(config)
+    if config["data"].get("device_transforms", False):      # opt-in: the workers decode, the GPU crops, resizes, normalises and stacks
+        tf = raw_frame_spec(config["data"]["crop"], config["model"]["representation_network"]["target_input_size"], 0)
+    else:
+        tf = final_transform(config)
     return {k: VideoDataset(path, batching, tf, allowed) for k, (path, batching, allowed) in generate_splits(config).items()}
