@@ -278,6 +278,24 @@ int caddy_debug_frames_plan(caddy_ctx* ctx, int* plan5);
  * One launch on the context's stream; waits for nothing, allocates nothing, deterministic.  Errors (-2, caddy_last_error): a context of another kind, null or misaligned
  * pointers, n_frames > max_frames, n_frames or n_slots < 1, mode other than 0 or 1. */
 int caddy_frames_to_observations(caddy_ctx* ctx, const unsigned char* frames, int n_frames, const int* slot_src, int n_slots, int mode, float* out);    /* dataset/batching.py:97-112 */
+/* The frame writer, the output side of the same context (an identity geometry, src = out and no crop, serves callers that have no source frames): fp32 planar frames in, uint8
+ * interleaved frames out -- on the device what the host does to every roll-out before it writes PNGs (evaluation/evaluation_dataset_builder.py:60-81,140-153: pad with the first
+ * ground-truth frame, (x + 1) / 2 when the minimum is negative, * 255, astype(uint8)) and to every played frame (play.py:140).
+ *   rec = (B, Trec, 3, out_h, out_w) fp32 on the device, contiguous.  first (nullable) = B planar 3 x out_h x out_w frames, frame b at first + b * first_stride floats (so it may
+ *   point at channels 0..2 of t = 0 of a (B, T, 3 S, H, W) observation tensor); when given it is sequence position 0 and T = Trec + 1, else T = Trec.
+ *   out_u8 (nullable) = (B, T, out_h, out_w, 3) uint8; out_f32 (nullable) = (B, T, 3, out_h, out_w) fp32 holding the context's mode-1 table value (x / 255) of every byte, i.e.
+ *   evaluation_transform of the PNG the host path would have written.  At least one of the two.
+ *   map: 0 = the values are in [0, 1] already; 1 = (x + 1) / 2 (play.py:140); 2 = the builder's rule (evaluation_dataset_builder.py:140-153), (x + 1) / 2 only if the minimum over
+ *   all B * T frames, `first` included, is negative -- decided on the device by a reduction launch whose flags the writer launch reads; a NaN anywhere means no mapping (torch.min
+ *   returns NaN and NaN < 0 is false), -0.0 is not negative.
+ *   Arithmetic, each operation rounded to fp32 and nothing contracted: v = x or (x + 1.0f) * 0.5f; s = v * 255.0f; byte = (int)s for 0 <= s < 256.  Where the host's cast is
+ *   undefined the byte saturates: s < 0 -> 0, s >= 256 -> 255, NaN -> 0, and the value is counted.
+ * One launch for map 0 and 1, two for map 2, on the context's stream; waits for nothing, allocates nothing, deterministic.  Errors (-2, caddy_last_error): a context of another
+ * kind, a null rec, pointers that are not 4-byte aligned, both outputs null, B or Trec < 1, B * T > max_frames, first_stride < 3 out_h out_w with B > 1, map outside 0..2. */
+int caddy_frames_write(caddy_ctx* ctx, const float* rec, int B, int Trec, const float* first, long first_stride, int map, unsigned char* out_u8, float* out_f32);    /* evaluation/evaluation_dataset_builder.py:60-81 */
+/* stats3 (host memory) receives, for the last caddy_frames_write: whether the values were mapped (1 / 0), the values that saturated (s < 0 or s >= 256) and the NaNs, over
+ * all 3 out_h out_w B T values.  Waits for the stream. */
+int caddy_frames_write_stats_get(caddy_ctx* ctx, unsigned* stats3);                                                                                                  /* evaluation/evaluation_dataset_builder.py:140-153 */
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

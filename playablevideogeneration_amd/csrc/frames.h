@@ -1,4 +1,4 @@
-// Device-side frame pipeline (frames.hip): uint8 frames -> the model's observation tensor.  What a FRAMES context keeps besides the scaffold of eval_ctx.h.
+// Device-side frame pipeline (frames.hip): uint8 frames -> the model's observation tensor, and the frame writer: fp32 planar frames -> uint8 interleaved frames.  What a FRAMES context keeps besides the scaffold of eval_ctx.h.
 #pragma once
 #include "net.h"
 
@@ -19,5 +19,6 @@ struct FramesState {
     float lut[512] = {};          // byte -> value, mode 0 then mode 1
     int *d_xb = nullptr, *d_xk = nullptr, *d_yb = nullptr, *d_yk = nullptr, *d_blk = nullptr;      // device copies (persistent arena)
     float* d_lut = nullptr;
+    unsigned* d_wstats = nullptr; // frame writer (caddy_frames_write): FW_WORDS device words -- the two flags of the map-2 reduction, the counts and the decision of the last call
 };
 void frames_free(caddy_ctx* c);      // releases caddy_ctx::frs (caddy_ctx_destroy)

@@ -19,6 +19,8 @@
 //   3. vertical pass + table + store: (output row, group of 4 outputs) per thread reads three LDS dwords per tap (lane stride 12 bytes: conflict-free), looks the 12 bytes up
 //              in the LDS copy of the table and stores one 16-byte vector per channel plane; the last group of a row with W % 4 != 0 stores scalars.
 // R is the largest of 16, 8, 4, 2, 1 whose rows fit 64 KiB of LDS; a plan within 16 KiB runs the 16 KiB variant of the kernel (more workgroups per CU).
+//
+// The same context also runs the output side, the frame writer (caddy_frames_write, further down): fp32 planar frames -> the uint8 interleaved frames the host would write.
 #include "eval_ctx.h"
 #include "frames.h"
 #include <cmath>
@@ -162,6 +164,127 @@ __global__ __launch_bounds__(FR_THREADS) void k_frames(FrArgs a) {
     }
 }
 
+// ---- Frame writer: fp32 planar frames -> uint8 interleaved frames (caddy_frames_write) ----
+// Reference: evaluation/evaluation_dataset_builder.py:60-81,140-153 (torch.cat([first, rec]) -> (x + 1) / 2 when torch.min is negative -> numpy * 255 -> astype(uint8)) and
+// play.py:140.  One lane takes 4 consecutive pixels of a row: three 16-byte loads (one per plane), 12 bytes packed into three dwords and stored contiguously (a wave writes 768
+// contiguous bytes), or, for the fp32 output, the mode-1 table value of every byte as one 16-byte store per plane.  The last group of a row with W % 4 != 0 loads and stores
+// scalars; a group whose 12 bytes do not start at a 4-byte boundary (odd W: row and frame bases at any byte) stores bytes.  Memory-bound, no LDS.
+enum { FW_NEG = 0, FW_NAN = 1, FW_SATURATED = 2, FW_NANS = 3, FW_MAPPED = 4, FW_WORDS = 8 };
+constexpr int FW_THREADS = 256, FW_SCAN_BLOCKS = 2048;
+
+struct FwArgs {
+    const float *rec, *first; long first_stride, rec_floats, first_floats, frame_floats;
+    int N, Trec, T, H, W, ngx, groups_per_frame, map;
+    const float* lut; unsigned* stats; uint8_t* out_u8; float* out_f32;
+};
+
+// map 2, first launch: is any value negative, is any a NaN?  (-0.0 < 0 and NaN < 0 are false, as on the host.)  The virtual array is rec followed by the B frames of `first`.
+__global__ __launch_bounds__(FW_THREADS) void k_frame_writer_scan(FwArgs a) {
+    const long n = a.rec_floats + a.first_floats, n4 = (n + 3) >> 2;
+    bool neg = false, nan = false;
+    for (long i = (long)blockIdx.x * FW_THREADS + threadIdx.x; i < n4; i += (long)gridDim.x * FW_THREADS) {
+        const long e = i * 4;
+        if (e + 4 <= a.rec_floats) {
+            const f32x4u v = *(const f32x4u*)(a.rec + e);
+            neg |= v.x < 0.f || v.y < 0.f || v.z < 0.f || v.w < 0.f;
+            nan |= v.x != v.x || v.y != v.y || v.z != v.z || v.w != v.w;
+        } else {
+            for (long j = e; j < e + 4 && j < n; j++) {
+                float x;
+                if (j < a.rec_floats) x = a.rec[j];
+                else { const long k = j - a.rec_floats, b = k / a.frame_floats; x = a.first[b * a.first_stride + (k - b * a.frame_floats)]; }
+                neg |= x < 0.f;
+                nan |= x != x;
+            }
+        }
+    }
+    if (neg) atomicOr(a.stats + FW_NEG, 1u);
+    if (nan) atomicOr(a.stats + FW_NAN, 1u);
+}
+
+// the host's expression, operation by operation: nothing here may be contracted or reassociated (x * 127.5f + 127.5f differs at level boundaries)
+__device__ __forceinline__ uint32_t fw_byte(float x, bool mapped, unsigned& saturated, unsigned& nans) {
+#pragma clang fp contract(off)
+    float v = x;
+    if (mapped) { v = x + 1.0f; v = v * 0.5f; }
+    const float s = v * 255.0f;
+    if (s != s) { nans++; return 0u; }
+    if (s < 0.0f) { saturated++; return 0u; }
+    if (s >= 256.0f) { saturated++; return 255u; }
+    return (uint32_t)(int)s;
+}
+
+// one group of frame n: row y, pixels [4 xg, 4 xg + cnt)
+__device__ __forceinline__ void writer_group(const FwArgs& a, bool mapped, int n, int y, int xg, int cnt, int lead, long plane, unsigned& saturated, unsigned& nans) {
+    const int H = a.H, W = a.W;
+    const int b = n / a.T, t = n - b * a.T;
+    const float* src = (lead && t == 0) ? a.first + (long)b * a.first_stride : a.rec + ((long)b * a.Trec + (t - lead)) * a.frame_floats;
+    src += (long)y * W + 4 * xg;
+    float x[3][4];
+    if (cnt == 4) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const f32x4u v = *(const f32x4u*)(src + c * plane);
+            x[c][0] = v.x; x[c][1] = v.y; x[c][2] = v.z; x[c][3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) x[c][j] = j < cnt ? src[c * plane + j] : 0.f;
+    }
+    uint32_t q[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) q[c][j] = j < cnt ? fw_byte(x[c][j], mapped, saturated, nans) : 0u;
+    if (a.out_u8) {
+        uint8_t* o = a.out_u8 + (((long)n * H + y) * W + 4 * xg) * 3;
+        if (cnt == 4 && ((uintptr_t)o & 3) == 0) {
+            uint32_t d[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) d[(3 * j + c) >> 2] |= q[c][j] << (8 * ((3 * j + c) & 3));      // byte 3 j + c of the group is channel c of its pixel j
+            uint32_t* o4 = (uint32_t*)o;
+            o4[0] = d[0]; o4[1] = d[1]; o4[2] = d[2];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (j < cnt) { o[3 * j] = (uint8_t)q[0][j]; o[3 * j + 1] = (uint8_t)q[1][j]; o[3 * j + 2] = (uint8_t)q[2][j]; }
+        }
+    }
+    if (a.out_f32) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float* o = a.out_f32 + (((long)n * 3 + c) * H + y) * W + 4 * xg;
+            if (cnt == 4) {
+                f32x4u v = {a.lut[q[c][0]], a.lut[q[c][1]], a.lut[q[c][2]], a.lut[q[c][3]]};
+                *(f32x4u*)o = v;
+            } else {
+                o[0] = a.lut[q[c][0]];
+                if (cnt > 1) o[1] = a.lut[q[c][1]];
+                if (cnt > 2) o[2] = a.lut[q[c][2]];
+            }
+        }
+    }
+}
+
+// grid: x = blocks of FW_THREADS groups inside a frame, y = frames (a frame loop past 65535)
+__global__ __launch_bounds__(FW_THREADS) void k_frame_writer(FwArgs a) {
+    const bool mapped = a.map == 1 || (a.map == 2 && a.stats[FW_NEG] != 0u && a.stats[FW_NAN] == 0u);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.stats[FW_MAPPED] = mapped ? 1u : 0u;
+    const int r = blockIdx.x * FW_THREADS + threadIdx.x;
+    if (r >= a.groups_per_frame) return;
+    const int H = a.H, W = a.W, y = r / a.ngx, xg = r - y * a.ngx, lead = a.first ? 1 : 0;
+    const long plane = (long)H * W;
+    const int cnt = W - 4 * xg < 4 ? W - 4 * xg : 4;
+    unsigned saturated = 0, nans = 0;
+    for (int n = blockIdx.y; n < a.N; n += gridDim.y) writer_group(a, mapped, n, y, xg, cnt, lead, plane, saturated, nans);
+    if (saturated) atomicAdd(a.stats + FW_SATURATED, saturated);
+    if (nans) atomicAdd(a.stats + FW_NANS, nans);
+}
+
 // PIL's precompute_coeffs + normalize_coeffs_8bpc for the bilinear filter, in double and without contraction: (int)(0.5 + w 2^22) must not become one fused operation
 void axis_table(int in, int out, FrAxis* t) {
 #pragma clang fp contract(off)
@@ -268,6 +391,7 @@ EvalKind frames_kind(const FrGeomArgs& g) {
                 s->d_yk = (int*)c->persist.alloc(sizeof(int) * s->ax[1].kk.size());
                 s->d_blk = (int*)c->persist.alloc(sizeof(int) * s->blk.size());
                 s->d_lut = (float*)c->persist.alloc(sizeof(float) * 512);
+                s->d_wstats = (unsigned*)c->persist.alloc(sizeof(unsigned) * FW_WORDS);
             },
             [](caddy_ctx*) {},
             "caddy_frames_workspace_bytes"};
@@ -339,5 +463,42 @@ int caddy_frames_to_observations(caddy_ctx* c, const unsigned char* frames, int 
     else hipLaunchKernelGGL(k_frames<FR_LDS_LARGE>, grid, block, 0, c->stream, a);
     c->ck(hipGetLastError() == hipSuccess ? 0 : -1, "frame pipeline");
     return finish(c, "caddy_frames_workspace_bytes");
+}
+int caddy_frames_write(caddy_ctx* c, const float* rec, int B, int Trec, const float* first, long first_stride, int map, unsigned char* out_u8, float* out_f32) {
+    if (!ctx_needs(c, CTX_FRAMES, "caddy_frames_write")) return -2;
+    c->fail = false;
+    if (!rec) { set_error("null input"); return -2; }
+    if (!out_u8 && !out_f32) { set_error("caddy_frames_write: out_u8 and out_f32 are both null"); return -2; }
+    if (((uintptr_t)rec & 3) || ((uintptr_t)first & 3) || ((uintptr_t)out_u8 & 3) || ((uintptr_t)out_f32 & 3)) { set_error("caddy_frames_write: rec, first, out_u8 and out_f32 must be 4-byte aligned"); return -2; }
+    if (map < 0 || map > 2) { set_error("caddy_frames_write: map must be 0 (values in [0, 1]), 1 ((x + 1) / 2) or 2 ((x + 1) / 2 when the minimum is negative)"); return -2; }
+    if (B < 1 || Trec < 1) { set_error("caddy_frames_write: B and Trec must be positive"); return -2; }
+    const FramesState* s = c->frs;
+    const long T = (long)Trec + (first ? 1 : 0), N = (long)B * T, frame_floats = 3L * s->H * s->W;
+    if (N > c->cfg.batch) { set_error("caddy_frames_write: " + std::to_string(N) + " frames, the context was created for " + std::to_string(c->cfg.batch)); return -2; }
+    if (first && B > 1 && first_stride < frame_floats) { set_error("caddy_frames_write: first_stride below one frame (3 height width floats)"); return -2; }
+    FwArgs a{};
+    a.rec = rec; a.first = first; a.first_stride = first ? first_stride : 0; a.frame_floats = frame_floats;
+    a.rec_floats = (long)B * Trec * frame_floats; a.first_floats = first ? (long)B * frame_floats : 0;
+    a.Trec = Trec; a.T = (int)T; a.H = s->H; a.W = s->W; a.ngx = (s->W + 3) >> 2; a.map = map;
+    a.N = (int)N; a.groups_per_frame = s->H * a.ngx;      // (sides <= 32768: below 2^31)
+    a.lut = s->d_lut + 256; a.stats = s->d_wstats; a.out_u8 = out_u8; a.out_f32 = out_f32;
+    const dim3 grid((unsigned)((a.groups_per_frame + FW_THREADS - 1) / FW_THREADS), (unsigned)std::min<long>(N, 65535));
+    hipMemsetAsync(s->d_wstats, 0, sizeof(unsigned) * FW_WORDS, c->stream);
+    if (map == 2) {
+        const long n4 = (a.rec_floats + a.first_floats + 3) >> 2, want = (n4 + FW_THREADS - 1) / FW_THREADS;
+        hipLaunchKernelGGL(k_frame_writer_scan, dim3((unsigned)std::min<long>(want, FW_SCAN_BLOCKS)), dim3(FW_THREADS), 0, c->stream, a);
+    }
+    hipLaunchKernelGGL(k_frame_writer, grid, dim3(FW_THREADS), 0, c->stream, a);
+    c->ck(hipGetLastError() == hipSuccess ? 0 : -1, "frame writer");
+    return finish(c, "caddy_frames_workspace_bytes");
+}
+int caddy_frames_write_stats_get(caddy_ctx* c, unsigned* stats3) {
+    if (!ctx_needs(c, CTX_FRAMES, "caddy_frames_write_stats_get")) return -2;
+    if (!stats3) { set_error("null input"); return -2; }
+    unsigned v[FW_WORDS];
+    hipMemcpyAsync(v, c->frs->d_wstats, sizeof(v), hipMemcpyDeviceToHost, c->stream);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { set_error("caddy_frames_write_stats_get: reading the counts failed"); return -1; }
+    stats3[0] = v[FW_MAPPED]; stats3[1] = v[FW_SATURATED]; stats3[2] = v[FW_NANS];
+    return 0;
 }
 }

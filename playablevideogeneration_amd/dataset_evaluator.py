@@ -1,5 +1,6 @@
 """Dataset evaluation: a reference dataset against a generated one (evaluation/dataset_evaluator.py:29-256), the `config["evaluation"]["evaluator"]`
 seam of evaluate_dataset.py (factory `evaluator(config, logger, reference_dataset, generated_dataset)`, `.compute_metrics()` -> the dict written to data.yml).
+The factory's optional `batches=` takes ready (reference, generated) batch pairs in place of the two datasets (model_evaluation.ModelRollouts: `evaluate-model`).
 
 Per frame, on the device: mse, motion_masked_mse, psnr, ssim and -- when VGG19 weights are configured (`evaluation.vgg19_weights` or
 `evaluation.vgg19_from_torchvision`, the loader of Trainer._find_vgg_weights) -- vgg_sim, all from one fused HIP pass (metrics.FrameMetrics).  The
@@ -26,27 +27,25 @@ from . import metrics as M
 METRICS = ("mse", "motion_masked_mse", "psnr", "ssim", "vgg_sim")
 
 
+def batch_observations(batch) -> torch.Tensor:
+    """the observations of one batch: a batch that already lives on the device (model_evaluation.DeviceBatch) hands its tensor over as it is, every other
+    batch its host tensor"""
+    observations = getattr(batch, "device_observations", None)
+    return observations if observations is not None else batch.to_tuple(cuda=False)[0]
+
+
 class DatasetEvaluator:
     NOT_COMPUTED = ("- lpips, fid, fvd, inception score, detection metrics, action variance / accuracy and plots are not computed: "
                     "they need pretrained networks or detectors that are not available")
 
-    def __init__(self, config, logger, reference_dataset, generated_dataset):
-        from torch.utils.data import DataLoader
-        from .batching import collate_fn_for, single_batch_elements_collate_fn
+    def __init__(self, config, logger, reference_dataset, generated_dataset, batches=None):
+        """batches: an iterable with __len__ of ready (reference_batch, generated_batch) pairs (model_evaluation.ModelRollouts) that takes the place of the two datasets"""
         from .trainer import Trainer
         self.config, self.logger = config, logger
         self.reference_dataset, self.generated_dataset = reference_dataset, generated_dataset
-        b = config["evaluation"]["batching"]
-
-        def collate(ds):      # raw elements (evaluation.device_transforms) bring their own collate function
-            return (collate_fn_for(ds[0]) if len(ds) else None) or single_batch_elements_collate_fn
-        self.reference_dataloader = DataLoader(reference_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=collate(reference_dataset),
-                                               num_workers=b.get("num_workers", 0), pin_memory=torch.cuda.is_available())
-        self.generated_dataloader = DataLoader(generated_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=collate(generated_dataset),
-                                               num_workers=b.get("num_workers", 0), pin_memory=torch.cuda.is_available())
-        if len(self.reference_dataloader) != len(self.generated_dataloader):
-            raise Exception(f"Reference and generated datasets should have the same sequences, but their length differs:"
-                            f"Reference ({len(self.reference_dataloader)}), Generated({len(self.generated_dataloader)})")
+        self.batches = batches
+        if batches is None:
+            self._make_dataloaders(config["evaluation"]["batching"], reference_dataset, generated_dataset)
         self.vgg_state = Trainer._find_vgg_weights(config["evaluation"])
         if self.vgg_state is None:
             self.logger.print("- vgg_sim skipped: no VGG19 weights configured (evaluation.vgg19_weights / evaluation.vgg19_from_torchvision)")
@@ -78,6 +77,26 @@ class DatasetEvaluator:
             self.logger.print("- fvd is computed (I3D weights configured): the line above applies to it no longer")
         if self.is_state is not None:
             self.logger.print("- is is computed (Inception weights configured): the line above applies to it no longer")
+
+    def _make_dataloaders(self, b, reference_dataset, generated_dataset):
+        from torch.utils.data import DataLoader
+        from .batching import collate_fn_for, single_batch_elements_collate_fn
+
+        def collate(ds):      # raw elements (evaluation.device_transforms) bring their own collate function
+            return (collate_fn_for(ds[0]) if len(ds) else None) or single_batch_elements_collate_fn
+        self.reference_dataloader = DataLoader(reference_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=collate(reference_dataset),
+                                               num_workers=b.get("num_workers", 0), pin_memory=torch.cuda.is_available())
+        self.generated_dataloader = DataLoader(generated_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=collate(generated_dataset),
+                                               num_workers=b.get("num_workers", 0), pin_memory=torch.cuda.is_available())
+        if len(self.reference_dataloader) != len(self.generated_dataloader):
+            raise Exception(f"Reference and generated datasets should have the same sequences, but their length differs:"
+                            f"Reference ({len(self.reference_dataloader)}), Generated({len(self.generated_dataloader)})")
+
+    def batch_pairs(self):
+        """-> (number of batches, iterable of (reference_batch, generated_batch)): the two DataLoaders side by side, or the pairs handed in as `batches`"""
+        if self.batches is not None:
+            return len(self.batches), self.batches
+        return len(self.reference_dataloader), zip(self.reference_dataloader, self.generated_dataloader)
 
     @staticmethod
     def check_range(values: Dict[str, torch.Tensor], which: str):
@@ -158,12 +177,12 @@ class DatasetEvaluator:
     def compute_metrics(self) -> Dict:
         names = self.metric_names(METRICS)
         acc = {m: [] for m in names}
-        batches = len(self.reference_dataloader)
+        batches, pairs = self.batch_pairs()
         with torch.no_grad():
-            for idx, (reference_batch, generated_batch) in enumerate(zip(self.reference_dataloader, self.generated_dataloader)):
+            for idx, (reference_batch, generated_batch) in enumerate(pairs):
                 self.logger.print(f"- Computing metrics for batch [{idx}/{batches}]")
-                reference_observations = reference_batch.to_tuple(cuda=False)[0]
-                generated_observations = generated_batch.to_tuple(cuda=False)[0]
+                reference_observations = batch_observations(reference_batch)
+                generated_observations = batch_observations(generated_batch)
                 values = self.frame_values(reference_observations, generated_observations)
                 self.check_range(values, "ref")
                 self.check_range(values, "gen")
@@ -223,12 +242,12 @@ class ActionSpaceEvaluator(DatasetEvaluator):
         acc = {m: [] for m in names}
         detections, actions, movements = {}, [], []
         device = M.device()
-        batches = len(self.reference_dataloader)
+        batches, pairs = self.batch_pairs()
         with torch.no_grad():
-            for idx, (reference_batch, generated_batch) in enumerate(zip(self.reference_dataloader, self.generated_dataloader)):
+            for idx, (reference_batch, generated_batch) in enumerate(pairs):
                 self.logger.print(f"- Computing metrics for batch [{idx}/{batches}]")
-                reference_observations = reference_batch.to_tuple(cuda=False)[0].to(device)
-                generated_observations = generated_batch.to_tuple(cuda=False)[0].to(device)
+                reference_observations = batch_observations(reference_batch).to(device)
+                generated_observations = batch_observations(generated_batch).to(device)
                 values = self.frame_values(reference_observations, generated_observations)
                 self.check_range(values, "ref")
                 self.check_range(values, "gen")
@@ -260,5 +279,5 @@ class ActionSpaceEvaluator(DatasetEvaluator):
         return results
 
 
-def evaluator(config, logger, reference_dataset, generated_dataset):
-    return DatasetEvaluator(config, logger, reference_dataset, generated_dataset)
+def evaluator(config, logger, reference_dataset, generated_dataset, batches=None):
+    return DatasetEvaluator(config, logger, reference_dataset, generated_dataset, batches)

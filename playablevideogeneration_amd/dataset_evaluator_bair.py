@@ -24,5 +24,5 @@ class DatasetEvaluatorBair(ActionSpaceEvaluator):
         return np.asarray(out)
 
 
-def evaluator(config, logger, reference_dataset, generated_dataset):
-    return DatasetEvaluatorBair(config, logger, reference_dataset, generated_dataset)
+def evaluator(config, logger, reference_dataset, generated_dataset, batches=None):
+    return DatasetEvaluatorBair(config, logger, reference_dataset, generated_dataset, batches)

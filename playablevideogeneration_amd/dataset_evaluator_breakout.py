@@ -29,5 +29,5 @@ class DatasetEvaluatorBreakout(ActionSpaceEvaluator):
         return A.detection_metric_1d(detections["reference"], detections["generated"], "detection")
 
 
-def evaluator(config, logger, reference_dataset, generated_dataset):
-    return DatasetEvaluatorBreakout(config, logger, reference_dataset, generated_dataset)
+def evaluator(config, logger, reference_dataset, generated_dataset, batches=None):
+    return DatasetEvaluatorBreakout(config, logger, reference_dataset, generated_dataset, batches)

@@ -6,6 +6,7 @@ display / wandb / ffmpeg plumbing, on the plugin seam the reference itself uses 
     python -m playablevideogeneration_amd.drivers interpolate --config cfg.yaml --first 1 --second 2 [--steps 6] [--frames 8]
     python -m playablevideogeneration_amd.drivers build-dataset --config cfg.yaml
     python -m playablevideogeneration_amd.drivers evaluate      --config eval.yaml
+    python -m playablevideogeneration_amd.drivers evaluate-model --config cfg.yaml
 
     train        train.py:76-108      epochs of trainer.train_epoch, `latest` checkpoint after each, `checkpoint_<step>` every save_freq steps, evaluation with the inferred
                                       actions every eval_freq steps and -- when the data carries annotations -- with the ground-truth actions mapped through the Hungarian
@@ -18,6 +19,11 @@ display / wandb / ffmpeg plumbing, on the plugin seam the reference itself uses 
     evaluate     evaluate_dataset.py:22-64  an EVALUATION config (configs/evaluation/*.yaml: reference_data / generated_data / data.target_input_size /
                                       evaluation.batching): both datasets through the evaluation transform, the `evaluator(config, logger, reference, generated)`
                                       factory of evaluation.evaluator (playablevideogeneration_amd.dataset_evaluator), its metrics as logging.output_root/run_name/data.yml
+
+    evaluate-model  (no counterpart)  build-dataset + evaluate in one process and without the PNG round trip (model_evaluation.py): the test split is rolled out, quantised on the
+                                      device exactly as build-dataset would write it and scored by the evaluator of evaluation.dataset_evaluator (default: the generic one) with
+                                      the evaluation.* keys `evaluate` reads; the metrics as <output_directory>/model_metrics.yml.  `play` and `interpolate` take
+                                      --device-frames: their frames are quantised on the GPU (csrc/frames.hip), the same bytes
 
 The configuration defaults and directory layout are those of utils/configuration.py:31-110.  The model runs on the GPU through libcaddy_hip.so; there is no CPU path
 (the `*_loop` functions take the model object so that the tests can drive them with the emulator build of the same kernels).
@@ -163,6 +169,15 @@ def frame_to_uint8(frame: torch.Tensor) -> np.ndarray:
     return (((frame + 1) / 2).permute(1, 2, 0).cpu().numpy() * 255).astype(np.uint8)
 
 
+def device_frames_to_uint8(model, frames: torch.Tensor) -> np.ndarray:
+    """(n, 3, H, W) in [-1, 1] -> (n, H, W, 3) uint8: frame_to_uint8 for n frames as one launch of the frame writer (frame_pipeline.FrameWriter, csrc/frames.hip);
+    only the bytes cross to the host"""
+    from .frame_pipeline import MAP_ALWAYS, cached_writer
+    n, _, H, W = frames.shape
+    writer = cached_writer(H, W, n, getattr(getattr(model, "module", model), "_lib", None), frames.device)
+    return writer(frames[None], map=MAP_ALWAYS)[0].cpu().numpy()
+
+
 def _first_observations(dataset, batch_size: int) -> torch.Tensor:
     """the first validation batch's observations (play.py:101-103, 118): (B, T, 3S, H, W)"""
     from torch.utils.data import DataLoader
@@ -172,9 +187,10 @@ def _first_observations(dataset, batch_size: int) -> torch.Tensor:
     raise Exception("the validation split is empty")
 
 
-def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], out_dir: Optional[str] = None, sequence_idx: int = 0) -> Dict:
+def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], out_dir: Optional[str] = None, sequence_idx: int = 0, device_frames: bool = False) -> Dict:
     """play.py:115-207 for ONE sequence: `actions` are what the user would type (1 .. actions_count; 0 = stop, implied at the end of the list).
-    -> {"frames": uint8 (n + 1, H, W, 3), "actions": [...], "timestamps": [...]}; frames / metadata written under <out_dir>/<sequence_idx>/ when out_dir is given."""
+    -> {"frames": uint8 (n + 1, H, W, 3), "actions": [...], "timestamps": [...]}; frames / metadata written under <out_dir>/<sequence_idx>/ when out_dir is given.
+    device_frames: the frames are quantised on the device (device_frames_to_uint8) instead of frame_to_uint8 -- the same bytes."""
     model.eval()
     seq_dir = None
     if out_dir is not None:
@@ -187,7 +203,7 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
         model.start_inference()
         t0 = None
         for i in range(len(actions) + 1):
-            img = frame_to_uint8(frame)
+            img = device_frames_to_uint8(model, frame[None])[0] if device_frames else frame_to_uint8(frame)
             if t0 is None:
                 t0 = time.time()
                 stamps.append(0)
@@ -212,9 +228,10 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
 
 
 def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, second_action: int, steps: int, frames_count: int, out_dir: Optional[str] = None,
-                     batched: bool = False) -> List[np.ndarray]:
+                     batched: bool = False, device_frames: bool = False) -> List[np.ndarray]:
     """interpolate.py:102-158: for each value in linspace(0, 1, steps + 1) one sequence of `frames_count` generate_next_interpolation calls from the same start.
-    batched: all steps + 1 sequences advance as one batch per frame (one graph launch instead of steps + 1)."""
+    batched: all steps + 1 sequences advance as one batch per frame (one graph launch instead of steps + 1).
+    device_frames: the frames are quantised on the device (device_frames_to_uint8), with `batched` all steps + 1 frames of a step in one launch -- the same bytes."""
     model.eval()
     sequences = []
     if batched:
@@ -226,7 +243,7 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
             frame = obs[:, :3]
             frames = []
             for i in range(frames_count + 1):
-                imgs = [frame_to_uint8(frame[si]) for si in range(n)]
+                imgs = list(device_frames_to_uint8(model, frame)) if device_frames else [frame_to_uint8(frame[si]) for si in range(n)]
                 frames.append(imgs)
                 if out_dir is not None:
                     from PIL import Image
@@ -244,7 +261,7 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
             frame = obs[:3]
             frames = []
             for i in range(frames_count + 1):
-                img = frame_to_uint8(frame)
+                img = device_frames_to_uint8(model, frame[None])[0] if device_frames else frame_to_uint8(frame)
                 frames.append(img)
                 if out_dir is not None:
                     from PIL import Image
@@ -333,10 +350,13 @@ def main(argv=None) -> int:
     p = sub.add_parser("train"); p.add_argument("--config", required=True); p.add_argument("--max-steps", type=int, default=None)
     p = sub.add_parser("play"); p.add_argument("--config", required=True); p.add_argument("--actions", required=True, help="comma-separated, 1-based as typed in play.py")
     p.add_argument("--out", default="play_results"); p.add_argument("--sample", default="0:0", help="batch_index:observation_index of the first validation batch")
+    p.add_argument("--device-frames", action="store_true", help="quantise the frames on the GPU (the same bytes)")
     p = sub.add_parser("interpolate"); p.add_argument("--config", required=True); p.add_argument("--first", type=int, required=True); p.add_argument("--second", type=int, required=True)
     p.add_argument("--steps", type=int, default=6); p.add_argument("--frames", type=int, default=8); p.add_argument("--out", default=None)
     p.add_argument("--batched", action="store_true", help="advance all steps + 1 sequences as one batch per frame")
+    p.add_argument("--device-frames", action="store_true", help="quantise the frames on the GPU (the same bytes); with --batched all sequences of a step in one launch")
     p = sub.add_parser("build-dataset"); p.add_argument("--config", required=True)
+    p = sub.add_parser("evaluate-model"); p.add_argument("--config", required=True)
     p = sub.add_parser("evaluate"); p.add_argument("--config", required=True)
     args = ap.parse_args(argv)
     if args.cmd == "evaluate":
@@ -355,15 +375,20 @@ def main(argv=None) -> int:
         n = build_dataset_loop(config, model, datasets, logger)
         logger.print(f"- {n} videos written to {config['logging']['evaluation_dataset_directory']}")
         return 0
+    if args.cmd == "evaluate-model":      # (like build-dataset, it goes on without a checkpoint)
+        model, datasets = _load_for_inference(config, logger, required=False)
+        from .model_evaluation import evaluate_model_loop
+        evaluate_model_loop(config, model, datasets, logger)
+        return 0
     model, datasets = _load_for_inference(config, logger)
     obs = _first_observations(datasets["validation"], config["evaluation"]["batching"]["batch_size"])
     if args.cmd == "play":
         b, o = (int(x) for x in args.sample.split(":"))
-        res = play_loop(model, obs[b, o].cuda(), [int(a) for a in args.actions.split(",") if a != ""], args.out)
+        res = play_loop(model, obs[b, o].cuda(), [int(a) for a in args.actions.split(",") if a != ""], args.out, device_frames=args.device_frames)
         logger.print(f"- {len(res['frames'])} frames written to {os.path.join(args.out, '0')}")
         return 0
     out = args.out or config["logging"]["interpolated_sequences"]
-    interpolate_loop(model, obs[0, 0].cuda(), args.first, args.second, args.steps, args.frames, out, batched=args.batched)
+    interpolate_loop(model, obs[0, 0].cuda(), args.first, args.second, args.steps, args.frames, out, batched=args.batched, device_frames=args.device_frames)
     logger.print(f"- {args.steps + 1} sequences written to {out}")
     return 0
 

@@ -7,7 +7,9 @@
 variations (evaluation/action_sampler.py:6-30, action_variation_sampler.py:6-25), temperature `gumbel_temperature_end`; the reconstruction is
 padded with the first ground-truth frame, mapped from [-1, 1] to [0, 1] when its minimum is negative, and written as one folder per sequence in
 the reference's dataset format (dataset/video.py:95-156): `NNNNN.png` frames + `actions.pkl`, `rewards.pkl`, `metadata.pkl`, `dones.pkl`.
-Nothing but the forward runs on the GPU; the forward is the same `caddy_forward_full` the training step uses.
+By default nothing but the forward runs on the GPU; the forward is the same `caddy_forward_full` the training step uses.  With `evaluation_dataset.device_quantise: true`
+the padding, the range mapping and the truncating cast run on the device too (frame_pipeline.FrameWriter, csrc/frames.hip) and only uint8 frames cross to the host: the same
+bytes, a quarter of the traffic.
 """
 import os
 import pickle
@@ -41,6 +43,13 @@ class EvaluationVideo:
             Image.fromarray(fr).save(os.path.join(path, f"{i:05d}.{extension}"))
 
 
+def sequence_metadata(actions: np.ndarray, encoded_mus: np.ndarray) -> List:
+    """the metadata list of one generated sequence: the inferred / encoded action of every transition (evaluation_dataset_builder.py:105-117)"""
+    meta = [{"model": "ours", "inferred_action": a, "encoded_action": mu} for a, mu in zip(actions.tolist(), encoded_mus.tolist())]
+    meta.append({"model": "ours"})                                                   # no information for the last sample
+    return meta
+
+
 class EvaluationDatasetBuilder:
     def __init__(self, config, dataset, logger, logger_prefix="test"):
         self.config, self.logger, self.logger_prefix, self.dataset = config, logger, logger_prefix, dataset
@@ -49,6 +58,7 @@ class EvaluationDatasetBuilder:
         self.action_variation_sampler = ZeroActionVariationSampler()
         self.temperature = config["training"]["gumbel_temperature_end"]
         self.batch_size = config["evaluation"]["batching"]["batch_size"]
+        self.device_quantise = bool(config["evaluation_dataset"].get("device_quantise", False))      # opt-in: pad, map and cast on the device (frame_pipeline.FrameWriter)
 
     def _batches(self):
         """DataLoader(dataset, batch_size, shuffle=False, collate_fn=single_batch_elements_collate_fn) for datasets of BatchElements
@@ -71,7 +81,10 @@ class EvaluationDatasetBuilder:
     def predictions_to_videos(self, images: np.ndarray, actions: np.ndarray, encoded_mus: np.ndarray) -> List[EvaluationVideo]:
         """(bs, T, H, W, C) images in [0, 1], (bs, T-1) inferred actions, (bs, T-1, Da) sampled action directions -> videos whose metadata
         carries the inferred / encoded action of every transition (evaluation_dataset_builder.py:83-123)"""
-        images = (images * 255).astype(np.uint8)
+        return self.bytes_to_videos((images * 255).astype(np.uint8), actions, encoded_mus)
+
+    def bytes_to_videos(self, images: np.ndarray, actions: np.ndarray, encoded_mus: np.ndarray) -> List[EvaluationVideo]:
+        """predictions_to_videos behind its cast: (bs, T, H, W, C) uint8 images"""
         bs, T = images.shape[:2]
         if actions.shape[0] != bs:
             raise Exception(f"Images have batch size {bs} but actions have batch size {actions.shape[0]}")
@@ -79,10 +92,21 @@ class EvaluationDatasetBuilder:
             raise Exception(f"Images have sequence length {T} but actions have sequence length {actions.shape[1]}")
         videos = []
         for b in range(bs):
-            meta = [{"model": "ours", "inferred_action": a, "encoded_action": mu} for a, mu in zip(actions[b].tolist(), encoded_mus[b].tolist())]
-            meta.append({"model": "ours"})                                           # no information for the last sample
-            videos.append(EvaluationVideo(images[b], [0] * T, [0] * T, meta, [False] * T))
+            videos.append(EvaluationVideo(images[b], [0] * T, [0] * T, sequence_metadata(actions[b], encoded_mus[b]), [False] * T))
         return videos
+
+    def quantise_on_device(self, model, observations: torch.Tensor, rec: torch.Tensor) -> torch.Tensor:
+        """(bs, T, H, W, 3) uint8 on the device: the first ground-truth frame + the reconstruction through check_and_normalize_range and the cast of
+        predictions_to_videos, bit for bit, as two launches of the frame writer; values the cast is undefined for are counted there and reported here"""
+        from .frame_pipeline import MAP_IF_NEGATIVE, cached_writer
+        bs, Trec, _, H, W = rec.shape
+        writer = cached_writer(H, W, bs * (Trec + 1), getattr(getattr(model, "module", model), "_lib", None), rec.device)
+        frames = writer(rec, first=observations.to(rec.device, rec.dtype), map=MAP_IF_NEGATIVE)
+        stats = writer.stats()
+        if (stats["saturated"] or stats["nan"]) and self.logger is not None:
+            self.logger.print(f"- Warning: {stats['saturated']} values outside the uint8 range after the range mapping (saturated to 0 / 255) and {stats['nan']} NaNs "
+                              f"(written as 0) in a batch of generated frames")
+        return frames
 
     def build(self, model, write: bool = True) -> List[EvaluationVideo]:
         all_videos: List[EvaluationVideo] = []
@@ -94,6 +118,10 @@ class EvaluationDatasetBuilder:
                 results = model(batch_tuple, ground_truth_observations_init=self.ground_truth_observations_init, action_sampler=OneHotActionSampler(),
                                 action_variation_sampler=self.action_variation_sampler, gumbel_temperature=self.temperature)
                 rec, selected_actions, sampled_dirs = results[0], results[5], results[11]
+                if self.device_quantise:
+                    all_videos.extend(self.bytes_to_videos(self.quantise_on_device(model, batch_tuple[0], rec).cpu().numpy(), selected_actions.cpu().numpy(),
+                                                           sampled_dirs.cpu().numpy()))
+                    continue
                 first = batch_tuple[0][:, 0:1, 0:3].to(rec.device, rec.dtype)           # pad with the first ground-truth frame
                 rec = self.check_and_normalize_range(torch.cat([first, rec], dim=1))
                 images = np.moveaxis(rec.cpu().numpy(), 2, -1)

@@ -4,7 +4,8 @@
     stacking / collate          dataset/batching.py:97-112           slot i of the (bs, T, 3 S, H, W) tensor is (b, t, s) in row-major order, newest frame first
 
 The host decodes every frame once and ships it as uint8 (`video_dataset.raw_frame_spec`, `batching.RawBatch`); `FramePipeline` runs the one kernel that does the
-rest.  The byte -> fp32 tables are computed here with the very expressions of the host transforms (`batching.normalize_frame`, `video_dataset.evaluation_transform`), so
+rest.  `FrameWriter` is the output side (evaluation/evaluation_dataset_builder.py:60-81,140-153, play.py:140): fp32 planar frames in, the uint8 interleaved frames the host
+would have written out, and / or their evaluation_transform, without leaving the device.  The byte -> fp32 tables are computed here with the very expressions of the host transforms (`batching.normalize_frame`, `video_dataset.evaluation_transform`), so
 both paths give the same bits by construction.  There is no torch fallback: the kernel of the library in use (libcaddy_hip.so, or the tests' host simulator) is the
 only implementation.
 """
@@ -29,6 +30,8 @@ def _bind(lib):
         lib.caddy_frames_tables_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.caddy_debug_frames_plan.argtypes = [C.c_void_p, C.c_void_p]
         lib.caddy_frames_to_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        lib.caddy_frames_write.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]
+        lib.caddy_frames_write_stats_get.argtypes = [C.c_void_p, C.c_void_p]
         lib._caddy_frames_bound = True
     return lib
 
@@ -110,3 +113,67 @@ def cached_pipeline(src_h: int, src_w: int, crop, target_size_wh, mode: int, n_f
     key = ("frames", id(lib), dev, int(src_h), int(src_w), crop_key, tuple(int(v) for v in target_size_wh), int(mode))
     room = max(64, 1 << (max(int(n_frames), 1) - 1).bit_length())
     return M._cached(key, None, lambda: FramePipeline(src_h, src_w, crop, target_size_wh, room, mode, lib, device), lambda fp: fp.max_frames < n_frames)
+
+
+MAP_NONE = 0            # the values are in [0, 1] already
+MAP_ALWAYS = 1          # (x + 1) / 2: play.py:140
+MAP_IF_NEGATIVE = 2     # (x + 1) / 2 when the minimum over everything is negative: evaluation_dataset_builder.py:140-153
+
+
+def _planar_frames(t: torch.Tensor, H: int, W: int) -> bool:
+    """do the (3, H, W) blocks at t[b, 0, :3] (5 dims) / t[b, :3] (4 dims) lie planar and dense in memory?"""
+    return t.stride(-1) == 1 and t.stride(-2) == W and t.stride(-3) == H * W and (t.shape[0] == 1 or t.stride(0) >= 3 * H * W)
+
+
+class FrameWriter(M._EvalContext):
+    """The frame writer on an identity-geometry FRAMES context for frames of height x width, at most `max_frames` per call.
+    `writer(rec, first=None, map=1, want_u8=True, want_f32=False)`: rec (B, Trec, 3, H, W) fp32; `first` -- (B, 3, H, W), (B, 1, 3, H, W) or a whole (B, T, 3 S, H, W)
+    observation tensor, whose channels 0..2 at t = 0 are read in place -- becomes sequence position 0.  -> (B, T, H, W, 3) uint8 and / or (B, T, 3, H, W) fp32 in [0, 1]
+    (one tensor, or the pair when both are wanted), on the device.  `stats()` -> {"mapped", "saturated", "nan"} of the last call."""
+
+    def __init__(self, height: int, width: int, max_frames: int, lib=None, device=None):
+        super().__init__(height, width, max_frames, lib, device)
+        self.lib = _bind(self.lib)
+        lut = value_tables()
+        self._create(lambda n, h, w: self.lib.caddy_frames_workspace_bytes(n, h, w, None, h, w),
+                     lambda n, h, w, ws, nbytes: self.lib.caddy_frames_ctx_create(n, h, w, None, h, w, lut.data_ptr(), ws, nbytes))
+
+    def __call__(self, rec: torch.Tensor, first: Optional[torch.Tensor] = None, map: int = MAP_ALWAYS, want_u8: bool = True, want_f32: bool = False):
+        if rec.dim() != 5 or rec.dtype != torch.float32 or tuple(rec.shape[2:]) != (3, self.H, self.W):
+            raise ValueError(f"expected (B, T, 3, {self.H}, {self.W}) fp32 frames, got {tuple(rec.shape)} {rec.dtype}")
+        if not (want_u8 or want_f32):
+            raise ValueError("neither the uint8 nor the fp32 frames are wanted")
+        rec = rec.to(self.device).contiguous()
+        B, Trec = int(rec.shape[0]), int(rec.shape[1])
+        first_ptr, first_stride = None, 0
+        if first is not None:
+            if first.dtype != torch.float32 or first.dim() not in (4, 5) or int(first.shape[0]) != B or tuple(first.shape[-2:]) != (self.H, self.W) or int(first.shape[-3]) < 3:
+                raise ValueError(f"expected {B} first frames of (3, {self.H}, {self.W}) fp32, got {tuple(first.shape)} {first.dtype}")
+            first = first.to(self.device)
+            if not _planar_frames(first, self.H, self.W):
+                first = (first[:, 0, :3] if first.dim() == 5 else first[:, :3]).contiguous()
+            first_ptr, first_stride = first.data_ptr(), int(first.stride(0))
+        T = Trec + (first is not None)
+        u8 = torch.empty(B, T, self.H, self.W, 3, dtype=torch.uint8, device=self.device) if want_u8 else None
+        f32 = torch.empty(B, T, 3, self.H, self.W, dtype=torch.float32, device=self.device) if want_f32 else None
+        self._stream()
+        self._check(self.lib.caddy_frames_write(self.ctx, rec.data_ptr(), B, Trec, first_ptr, first_stride, int(map), u8.data_ptr() if want_u8 else None,
+                                                f32.data_ptr() if want_f32 else None))
+        return (u8, f32) if want_u8 and want_f32 else (u8 if want_u8 else f32)
+
+    def stats(self):
+        """{"mapped": bool, "saturated": int, "nan": int} of the last call, counted on the device; waits for the stream"""
+        v = (C.c_uint * 3)()
+        self._stream()
+        self._check(self.lib.caddy_frames_write_stats_get(self.ctx, v))
+        return {"mapped": bool(v[0]), "saturated": int(v[1]), "nan": int(v[2])}
+
+
+def cached_writer(height: int, width: int, n_frames: int, lib=None, device=None) -> FrameWriter:
+    """the writer of this library, device and geometry, (re)created when it holds too few frames"""
+    lib = lib if lib is not None else M._default_lib
+    dev = str(device) if device is not None else str(M.device(lib))
+    key = ("frame_writer", id(lib), dev, int(height), int(width))
+    room = max(64, 1 << (max(int(n_frames), 1) - 1).bit_length())
+    return M._cached(key, None, lambda: FrameWriter(height, width, room, lib, device), lambda fw: fw.max_frames < n_frames)
+
