@@ -296,6 +296,36 @@ int caddy_frames_write(caddy_ctx* ctx, const float* rec, int B, int Trec, const 
 /* stats3 (host memory) receives, for the last caddy_frames_write: whether the values were mapped (1 / 0), the values that saturated (s < 0 or s >= 256) and the NaNs, over
  * all 3 out_h out_w B T values.  Waits for the stream. */
 int caddy_frames_write_stats_get(caddy_ctx* ctx, unsigned* stats3);                                                                                                  /* evaluation/evaluation_dataset_builder.py:140-153 */
+/* --- Evaluation example sheets (csrc/sheets.hip): the contact sheets the reference's evaluator saves first (evaluation/evaluator.py:115-147), composed on the device from the
+ *     fp32 tensors of the forward pass; only the finished image is left to copy.  A SHEETS context is an evaluation context of its own kind (no model, no weights) sized by the
+ *     largest sheet a call may ask for: max_rows rows of cells (two per drawn sequence) of max_cols cells (the sequence length).  Destroy with caddy_ctx_destroy.
+ *     Layout (torchvision make_grid(list, nrow = T, padding = 2, pad_value = 1)): R rows of T cells of h x w; the image is (R (h + 2) + 2, T (w + 2) + 2, 3) uint8 interleaved,
+ *     cell (r, t) starts at pixel (r (h + 2) + 2, t (w + 2) + 2) and every other pixel is 255. --- */
+size_t caddy_sheets_workspace_bytes(int max_rows, int max_cols);                                                                                                     /* evaluation/evaluator.py:115-147 */
+caddy_ctx* caddy_sheets_ctx_create(int max_rows, int max_cols, void* workspace, size_t bytes);                                                                       /* evaluation/evaluator.py:115-147 */
+/* obs = (B, T, channels, H, W) fp32 on the device, of which channels 0..2 are read; rec = (B, Trec, 3, h, w) fp32 on the device, Trec = T or T - 1, (H, W) = (h, w) times 1, 2 or 4;
+ * out_u8 = (2 min(B, 30) (h + 2) + 2, T (w + 2) + 2, 3) uint8 on the device.  Row 2 b is the ground truth of sequence b resized to h x w, row 2 b + 1 its reconstruction; with
+ * Trec = T - 1 column 0 of a reconstruction row is the (mapped) ground-truth frame 0 (save_examples, evaluator.py:392-436).
+ *   resize: F.interpolate(mode = "bilinear", align_corners = False) as the CPU computes it for these factors: a copy; ((0.25 a + 0.25 b) + 0.25 c) + 0.25 d over the source pixels
+ *   (2y, 2x), (2y, 2x + 1), (2y + 1, 2x), (2y + 1, 2x + 1); the same form over (4y + 1, 4x + 1), (4y + 1, 4x + 2), (4y + 2, 4x + 1), (4y + 2, 4x + 2).  Other ratios are refused.
+ *   range (check_and_normalize_range, evaluator.py:378-390): the resized ground truth and the reconstruction are each mapped by (x + 1) / 2 when their minimum over all B sequences
+ *   is negative; a NaN anywhere in a tensor means no mapping for it, -0.0 is not negative.  byte = (int)(v * 255.0f) with caddy_frames_write's arithmetic and saturation rules.
+ *   weighted != 0 (save_examples_with_weights, evaluator.py:314-376, with the mask of MotionLossWeightMaskCalculator.compute_weight_mask, training/losses.py:604-649, as both
+ *   weights; full resolution only): on the unmapped tensors m = 1 at t = 0 and, for t >= 1, m = ((d_0 + d_1) + d_2) + bias with d_c = |gt_t - gt_{t-1}| + |rec'_t - rec'_{t-1}|,
+ *   rec'_0 = gt_0 when Trec = T - 1; w = m / max |m| over all B sequences; col = lut768[3 min((int)(w * 256.0f), 255) + c]; v = (double)(x * 0.4f) + col * 0.6 on the mapped frame x;
+ *   byte = (int)(v * 255.0).  lut768 = 256 x 3 doubles on the device (matplotlib's viridis table), nullable when weighted = 0.  A NaN or a negative m is reported by
+ *   caddy_sheet_stats_get (the reference's assert weights_mask.min() >= 0); the image of such a call is not specified.
+ * Two launches (a reduction, then the compose launch that writes every byte of the image once, padding included) on the context's stream; waits for nothing, allocates nothing,
+ * deterministic.  Errors (-2, caddy_last_error): a context of another kind, null or misaligned pointers (4 bytes; lut768 8), sizes < 1, channels < 3, Trec not in {T, T - 1},
+ * a ratio other than 1, 2 or 4, weighted with (h, w) != (H, W) or a null lut768, more rows or columns than the context was created for. */
+int caddy_sheet_examples(caddy_ctx* ctx, const float* obs, int B, int T, int channels, int H, int W, const float* rec, int Trec, int h, int w, int weighted, float bias,
+                         const double* lut768, unsigned char* out_u8);                                                                                               /* evaluation/evaluator.py:392-436, 314-376 */
+/* frames = (n, T, 3, h, w) fp32 on the device; out_u8 = (n (h + 2) + 2, T (w + 2) + 2, 3) uint8 on the device: one row per sequence, as interpolate.py:102-158 lays its
+ * interpolation values out.  map: 0 = the values are in [0, 1] already, 1 = (x + 1) / 2 (caddy_frames_write's maps 0 and 1, the same bytes).  One launch.  Errors as above. */
+int caddy_sheet_strip(caddy_ctx* ctx, const float* frames, int n, int T, int h, int w, int map, unsigned char* out_u8);                                              /* interpolate.py:102-158 */
+/* stats5 (host memory) receives, for the last sheet: whether the ground truth and the reconstruction were mapped (1 / 0 each; the strip reports its map twice), the values that
+ * saturated, the NaNs (over the drawn cells), and whether the mask held a NaN or a negative value (evaluator.py:135).  Waits for the stream. */
+int caddy_sheet_stats_get(caddy_ctx* ctx, unsigned* stats5);                                                                                                         /* evaluation/evaluator.py:135 */
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

@@ -7,6 +7,7 @@
 #include "fid.h"
 #include "fvd.h"
 #include "frames.h"
+#include "sheets.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1680,6 +1681,7 @@ void caddy_ctx_destroy(caddy_ctx* c) {
     fid_free(c);
     fvd_free(c);
     frames_free(c);
+    sheets_free(c);
     delete c;
 }
 int caddy_set_stream(caddy_ctx* c, void* s) { c->stream = (hipStream_t)s; return 0; }

@@ -72,6 +72,7 @@ def finish_configuration(config: Dict, create_directories: bool = True) -> Dict:
     data.setdefault("ground_truth_available", True)
     ev.setdefault("eval_freq", 0)
     ev.setdefault("max_evaluation_batches", None)
+    ev.setdefault("save_examples", False)      # (this package: the evaluator writes the example sheets of evaluator.py:115-147, composed on the device)
     tr.setdefault("use_motion_weights", False)
     tr.setdefault("motion_weights_bias", 0.0)
     tr.setdefault("action_direction_plotting_freq", 1000)
@@ -228,12 +229,23 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
 
 
 def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, second_action: int, steps: int, frames_count: int, out_dir: Optional[str] = None,
-                     batched: bool = False, device_frames: bool = False) -> List[np.ndarray]:
+                     batched: bool = False, device_frames: bool = False, sheet: bool = False) -> List[np.ndarray]:
     """interpolate.py:102-158: for each value in linspace(0, 1, steps + 1) one sequence of `frames_count` generate_next_interpolation calls from the same start.
     batched: all steps + 1 sequences advance as one batch per frame (one graph launch instead of steps + 1).
-    device_frames: the frames are quantised on the device (device_frames_to_uint8), with `batched` all steps + 1 frames of a step in one launch -- the same bytes."""
+    device_frames: the frames are quantised on the device (device_frames_to_uint8), with `batched` all steps + 1 frames of a step in one launch -- the same bytes.
+    sheet: also <out_dir>/sheet.png, one row per interpolation value, composed on the device from the frames as generated (example_sheets.ExampleSheets.strip)."""
     model.eval()
     sequences = []
+    kept = []      # sheet: the fp32 frames, [frame index] -> (n, 3, H, W) (batched) or [sequence][frame index] -> (3, H, W)
+
+    def write_sheet(frames5):
+        from PIL import Image
+        from .example_sheets import MAP_ALWAYS, cached_sheets
+        n, T = int(frames5.shape[0]), int(frames5.shape[1])
+        image = cached_sheets(n, T, getattr(getattr(model, "module", model), "_lib", None), frames5.device).strip(frames5, MAP_ALWAYS)
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            Image.fromarray(image).save(os.path.join(out_dir, "sheet.png"))
     if batched:
         alphas = np.linspace(0.0, 1.0, steps + 1).tolist()
         n = len(alphas)
@@ -245,6 +257,8 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
             for i in range(frames_count + 1):
                 imgs = list(device_frames_to_uint8(model, frame)) if device_frames else [frame_to_uint8(frame[si]) for si in range(n)]
                 frames.append(imgs)
+                if sheet:
+                    kept.append(frame.detach().clone())
                 if out_dir is not None:
                     from PIL import Image
                     for si in range(n):
@@ -253,6 +267,8 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
                 if i == frames_count:
                     break
                 frame, obs = model.generate_next_interpolation_batch(obs, first_action, second_action, alphas)
+        if sheet:
+            write_sheet(torch.stack(kept, dim=1))
         return [np.stack([f[si] for f in frames], axis=0) for si in range(n)]
     with torch.no_grad():
         for si, alpha in enumerate(np.linspace(0.0, 1.0, steps + 1).tolist()):
@@ -263,6 +279,8 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
             for i in range(frames_count + 1):
                 img = device_frames_to_uint8(model, frame[None])[0] if device_frames else frame_to_uint8(frame)
                 frames.append(img)
+                if sheet:
+                    kept.append(frame.detach().clone())
                 if out_dir is not None:
                     from PIL import Image
                     os.makedirs(os.path.join(out_dir, str(si)), exist_ok=True)
@@ -271,6 +289,8 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
                     break
                 frame, obs = model.generate_next_interpolation(obs, first_action, second_action, alpha)
             sequences.append(np.stack(frames, axis=0))
+    if sheet:
+        write_sheet(torch.stack(kept).reshape(len(sequences), frames_count + 1, *kept[0].shape))
     return sequences
 
 
@@ -355,6 +375,7 @@ def main(argv=None) -> int:
     p.add_argument("--steps", type=int, default=6); p.add_argument("--frames", type=int, default=8); p.add_argument("--out", default=None)
     p.add_argument("--batched", action="store_true", help="advance all steps + 1 sequences as one batch per frame")
     p.add_argument("--device-frames", action="store_true", help="quantise the frames on the GPU (the same bytes); with --batched all sequences of a step in one launch")
+    p.add_argument("--sheet", action="store_true", help="also write <out>/sheet.png: one row per interpolation value, composed on the GPU")
     p = sub.add_parser("build-dataset"); p.add_argument("--config", required=True)
     p = sub.add_parser("evaluate-model"); p.add_argument("--config", required=True)
     p = sub.add_parser("evaluate"); p.add_argument("--config", required=True)
@@ -388,7 +409,7 @@ def main(argv=None) -> int:
         logger.print(f"- {len(res['frames'])} frames written to {os.path.join(args.out, '0')}")
         return 0
     out = args.out or config["logging"]["interpolated_sequences"]
-    interpolate_loop(model, obs[0, 0].cuda(), args.first, args.second, args.steps, args.frames, out, batched=args.batched, device_frames=args.device_frames)
+    interpolate_loop(model, obs[0, 0].cuda(), args.first, args.second, args.steps, args.frames, out, batched=args.batched, device_frames=args.device_frames, sheet=args.sheet)
     logger.print(f"- {args.steps + 1} sequences written to {out}")
     return 0
 

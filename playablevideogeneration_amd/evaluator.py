@@ -1,15 +1,18 @@
 """Headless counterpart of evaluation/evaluator.py (`config["evaluation"]["evaluator"] = "playablevideogeneration_amd.evaluator"`, train.py:56):
 the same quantities -- per-position observation / state losses of the gt_init = 1 roll-out, action entropies, direction KL, mutual
 information, Hungarian action accuracy and the ground-truth -> model action mapping -- computed from the HIP forward pass, without the
-reference's wandb / image-grid / plotting side effects (and without `sklearn.utils.linear_assignment_`, removed from sklearn >= 0.23:
+reference's wandb / plotting side effects (and without `sklearn.utils.linear_assignment_`, removed from sklearn >= 0.23:
 `scipy.optimize.linear_sum_assignment` gives the same optimum).  The per-position observation / state / perceptual losses come from the library's loss kernels
 (caddy_sequence_losses_per_frame, caddy_perceptual_per_frame: the VGG19 of the training loss, evaluator.py:55,62,193-197); the perceptual entries appear when the model
 carries VGG19 weights (trainer: `training.vgg19_weights` / `vgg19_from_torchvision`, or model.enable_perceptual(state_dict)).
+With `evaluation.save_examples: true` the first evaluated batch also yields the reference's example sheets (evaluator.py:115-147), composed on the device from that batch's
+forward pass (example_sheets.py, csrc/sheets.hip): <logging.output_images_directory>/{step:09}_observations_r{0,1,2}.png and {step:09}_motion_weighted_observations_.png.
 
     ev = evaluator(config, dataset, logger, action_sampler=None, logger_prefix="test")
     log_data = ev.evaluate(model, step)              # dict with the reference's keys: "<prefix>/observations_loss/pos_3", ".../actions_accuracy", ...
     ev.get_best_action_mappings()                    # {ground-truth action: model action}, feeds GroundTruthActionSampler
 """
+import os
 import sys
 from typing import Dict, List, Optional, Tuple
 
@@ -60,6 +63,7 @@ class Evaluator:
         ev = config.get("evaluation", {})
         self.batch_size = ev.get("batching", {}).get("batch_size", 8)
         self.max_evaluation_batches = ev.get("max_evaluation_batches", None)
+        self.save_examples = bool(ev.get("save_examples", False))
         self.action_sampler = action_sampler
         self.best_action_mappings: Optional[Dict[int, int]] = None
 
@@ -91,6 +95,25 @@ class Evaluator:
         acc = (reordered == ground_truth.to(reordered.dtype)).sum().item() / max(1, predictions.numel())
         return acc, {gt_i: int(model_i) for model_i, gt_i in match}
 
+    def save_example_sheets(self, model, observations: torch.Tensor, multiresolution_reconstructions, step: int) -> List[str]:
+        """evaluator.py:128-138 on the tensors of a forward pass: the ground truth / reconstruction sheet of every resolution and the motion-weighted sheet (bias:
+        training.motion_weights_bias) as PNGs in logging.output_images_directory.  Only rank 0 writes.  -> the paths written"""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+            return []
+        from PIL import Image
+        from .example_sheets import evaluation_sheets
+        directory = self.config["logging"]["output_images_directory"]
+        os.makedirs(directory, exist_ok=True)
+        say = self.logger.print if self.logger is not None else None
+        bias = float(self.config.get("training", {}).get("motion_weights_bias", 0.0))
+        lib = getattr(getattr(model, "module", model), "_lib", None)
+        written = []
+        for key, image in evaluation_sheets(observations.to(multiresolution_reconstructions[0].device), list(multiresolution_reconstructions), bias, lib, say).items():
+            written.append(os.path.join(directory, f"{step:09}_{key}.png"))
+            Image.fromarray(image).save(written[-1])
+        return written
+
     def evaluate(self, model, step: int) -> Dict[str, float]:
         sums: Dict[str, float] = {}
         counts: Dict[str, int] = {}
@@ -114,6 +137,8 @@ class Evaluator:
                 bt = _batch_tuple(batch)
                 r = model(bt, ground_truth_observations_init=1, action_sampler=self.action_sampler)
                 frames, states, rec_states, selected, logits, samples = r[0], r[3], r[2], r[5], r[6], r[7]
+                if self.save_examples and i == 0:      # the sheets of this batch's forward pass: no extra forward (evaluator.py:115-147 runs one of its own)
+                    self.save_example_sheets(model, bt[0], r[1], step)
                 ddist, r_logits = r[10], r[15]
                 eng = getattr(model.module if hasattr(model, "module") else model, "last_engine", None)
                 if eng is not None and hasattr(eng, "sequence_losses_per_frame"):      # per-frame sums from the loss kernels; positions = means over the batch
