@@ -326,6 +326,35 @@ int caddy_sheet_strip(caddy_ctx* ctx, const float* frames, int n, int T, int h, 
 /* stats5 (host memory) receives, for the last sheet: whether the ground truth and the reconstruction were mapped (1 / 0 each; the strip reports its map twice), the values that
  * saturated, the NaNs (over the drawn cells), and whether the mask held a NaN or a negative value (evaluator.py:135).  Waits for the stream. */
 int caddy_sheet_stats_get(caddy_ctx* ctx, unsigned* stats5);                                                                                                         /* evaluation/evaluator.py:135 */
+/* --- Device-side MJPEG video writer (csrc/video.hip): baseline JPEG files encoded on the device, in place of the reference's VideoSaver.save_video (utils/save_video_ffmpeg.py:
+ *     172-198; play.py:192, interpolate.py:147), whose ffmpeg is not available here; the AVI container is written on the host (video_writer.py).  A VIDEO context is an evaluation
+ *     context of its own kind (no model, no weights) for frames of H x W (each 1..4096) at `quality` 1..100; a call with more than max_frames frames runs in chunks.  Destroy
+ *     with caddy_ctx_destroy.  The file of a frame is byte for byte libjpeg's for that quality, 4:4:4 sampling, the Annex K Huffman tables, one interleaved scan (each MCU one Y,
+ *     one Cb, one Cr block) and no restart markers -- what Pillow's Image.save(f, format = "JPEG", quality = q, subsampling = 0, optimize = False) writes.  Marker order: SOI,
+ *     APP0 (JFIF 1.01, density unit 0, 1 x 1), two DQT, SOF0, four DHT, SOS, the scan, EOI.  All arithmetic is integer:
+ *       tables   scale = q < 50 ? 5000 / q : 200 - 2 q; entry = (base * scale + 50) / 100 clamped to 1..255 (Annex K base tables), computed on the host at creation
+ *       colour   (jccolor.c, FIX(x) = (int)(x * 65536 + 0.5))  Y = (FIX(.299) R + FIX(.587) G + FIX(.114) B + 32768) >> 16;
+ *                Cb = (-FIX(.16874) R - FIX(.33126) G + FIX(.5) B + (128 << 16) + 32767) >> 16;  Cr = (FIX(.5) R - FIX(.41869) G - FIX(.08131) B + (128 << 16) + 32767) >> 16
+ *       padding  the last column and the last row replicated up to the next multiple of 8; then - 128
+ *       DCT      jfdctint.c (CONST_BITS 13, PASS1_BITS 2): rows with << 2 / DESCALE(., 11), then columns with DESCALE(., 2) / DESCALE(., 15), DESCALE(x, n) = (x + (1 << (n - 1))) >> n
+ *       quantise d = table[k] << 3 (k in zigzag order): |c| -> (|c| + (d >> 1)) / d, truncating, the sign restored
+ *       entropy  (jchuff.c) diff = DC - the previous MCU's DC of that component within the frame (0 at its first MCU); for a value v: nbits = bit length of |v|, the code of
+ *                nbits (DC) or (run << 4) + nbits (AC), then the low nbits bits of (v < 0 ? v - 1 : v); 0xF0 for every 16 zeros of a longer run; EOB (0x00) only when the block
+ *                ends in zeros; table 0 for Y, table 1 for Cb and Cr; the scan padded with 1-bits to a byte; every 0xFF byte of the scan followed by 0x00 --- */
+size_t caddy_video_workspace_bytes(int max_frames, int H, int W);                                                                                                    /* utils/save_video_ffmpeg.py:172-198 */
+caddy_ctx* caddy_video_ctx_create(int max_frames, int H, int W, int quality, void* workspace, size_t bytes);                                                         /* utils/save_video_ffmpeg.py:172-198 */
+/* the output capacity no input of n frames of H x W can exceed: n (623 header bytes + 2 ceil(blocks (63 (16 + 10) + 11 + 11) / 8) + 2) with blocks = 3 ceil(H / 8) ceil(W / 8) --
+ * an AC symbol is at most 16 + 10 bits, a DC symbol 11 + 11, every byte may be stuffed.  0 (caddy_last_error) for sizes outside 1..4096 or n < 1. */
+size_t caddy_video_stream_bound(int n, int H, int W);                                                                                                                /* utils/save_video_ffmpeg.py:172-198 */
+/* frames_u8 = (n, H, W, 3) uint8 interleaved RGB on the device (what caddy_frames_write produces; any alignment); out_stream (device, out_capacity bytes) receives n complete
+ * files back to back; offsets (device, n + 1 words, 4-byte aligned) receives where each file starts and, last, the total length.  The caller copies the offsets and then
+ * out_stream[0, total) only.  Five launches per chunk of max_frames frames on the context's stream; waits for nothing, allocates nothing; the bits meet
+ * through atomicOr on zeroed words, which does not depend on the order, so a call is deterministic.  Errors (-2, caddy_last_error): a context of another kind, null pointers,
+ * misaligned offsets, n < 1, out_capacity < caddy_video_stream_bound(n, H, W) (nothing is written: never a truncated stream), a bound of 2^32 bytes or more. */
+int caddy_video_encode(caddy_ctx* ctx, const unsigned char* frames_u8, int n, unsigned char* out_stream, size_t out_capacity, unsigned* offsets);                    /* utils/save_video_ffmpeg.py:172-198 */
+/* tests: the host copies of what the context built (each nullable): the two quantisation tables in natural order, luminance first (128 bytes); the header SOI .. SOS;
+ * its length (623) */
+int caddy_video_tables_get(caddy_ctx* ctx, unsigned char* qtables128, unsigned char* header, int* header_bytes);                                                     /* utils/save_video_ffmpeg.py:172-198 */
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

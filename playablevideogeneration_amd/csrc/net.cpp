@@ -8,6 +8,7 @@
 #include "fvd.h"
 #include "frames.h"
 #include "sheets.h"
+#include "video.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1682,6 +1683,7 @@ void caddy_ctx_destroy(caddy_ctx* c) {
     fvd_free(c);
     frames_free(c);
     sheets_free(c);
+    video_free(c);
     delete c;
 }
 int caddy_set_stream(caddy_ctx* c, void* s) { c->stream = (hipStream_t)s; return 0; }

@@ -188,11 +188,15 @@ def _first_observations(dataset, batch_size: int) -> torch.Tensor:
     raise Exception("the validation split is empty")
 
 
-def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], out_dir: Optional[str] = None, sequence_idx: int = 0, device_frames: bool = False) -> Dict:
+def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], out_dir: Optional[str] = None, sequence_idx: int = 0, device_frames: bool = False,
+              video: bool = False, fps=5, video_quality: int = 90) -> Dict:
     """play.py:115-207 for ONE sequence: `actions` are what the user would type (1 .. actions_count; 0 = stop, implied at the end of the list).
     -> {"frames": uint8 (n + 1, H, W, 3), "actions": [...], "timestamps": [...]}; frames / metadata written under <out_dir>/<sequence_idx>/ when out_dir is given.
-    device_frames: the frames are quantised on the device (device_frames_to_uint8) instead of frame_to_uint8 -- the same bytes."""
+    device_frames: the frames are quantised on the device (device_frames_to_uint8) instead of frame_to_uint8 -- the same bytes.
+    video: also <out_dir>/<sequence_idx>/video.avi (play.py:192 at `fps` frames per second): the frames the PNGs hold, quantised and JPEG-encoded on the device
+    (video_writer.save_video)."""
     model.eval()
+    kept = []      # video: the fp32 frames as generated
     seq_dir = None
     if out_dir is not None:
         seq_dir = os.path.join(out_dir, str(sequence_idx))
@@ -211,6 +215,8 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
             else:
                 stamps.append(time.time() - t0)
             frames.append(img)
+            if video:
+                kept.append(frame.detach().clone())
             if seq_dir is not None:
                 from PIL import Image
                 Image.fromarray(img).save(os.path.join(seq_dir, f"{i}.png"))
@@ -222,6 +228,9 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
             done.append(a + 1)
             frame, obs = model.generate_next(obs, a)
     meta = {"actions": done, "timestamps": stamps}
+    if video and seq_dir is not None:
+        from .video_writer import save_video
+        save_video(model, torch.stack(kept), os.path.join(seq_dir, "video.avi"), fps, video_quality)
     if seq_dir is not None:
         with open(os.path.join(seq_dir, "play_metadata.pkl"), "wb") as f:
             pickle.dump(meta, f)
@@ -229,13 +238,30 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
 
 
 def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, second_action: int, steps: int, frames_count: int, out_dir: Optional[str] = None,
-                     batched: bool = False, device_frames: bool = False, sheet: bool = False) -> List[np.ndarray]:
+                     batched: bool = False, device_frames: bool = False, sheet: bool = False, video: bool = False, fps=5, video_quality: int = 90) -> List[np.ndarray]:
     """interpolate.py:102-158: for each value in linspace(0, 1, steps + 1) one sequence of `frames_count` generate_next_interpolation calls from the same start.
     batched: all steps + 1 sequences advance as one batch per frame (one graph launch instead of steps + 1).
     device_frames: the frames are quantised on the device (device_frames_to_uint8), with `batched` all steps + 1 frames of a step in one launch -- the same bytes.
-    sheet: also <out_dir>/sheet.png, one row per interpolation value, composed on the device from the frames as generated (example_sheets.ExampleSheets.strip)."""
+    sheet: also <out_dir>/sheet.png, one row per interpolation value, composed on the device from the frames as generated (example_sheets.ExampleSheets.strip).
+    video: also <out_dir>/<i>/video.avi per interpolation value (interpolate.py:147 at `fps` frames per second), the frames the PNGs hold, quantised and JPEG-encoded on the
+    device (video_writer.JpegEncoder); with `batched` all values' frames of one step in one call -- the same files."""
     model.eval()
     sequences = []
+    jpegs: Dict[int, List[bytes]] = {}      # video: [sequence] -> the encoded frames
+
+    def encode(frames4, first_sequence):
+        from .video_writer import cached_encoder
+        n, _, H, W = (int(v) for v in frames4.shape)
+        enc = cached_encoder(H, W, n, video_quality, getattr(getattr(model, "module", model), "_lib", None), frames4.device)
+        for k, data in enumerate(enc(frames4)):
+            jpegs.setdefault(first_sequence + k, []).append(data)
+
+    def write_videos(width, height):
+        from .video_writer import write_avi
+        if out_dir is not None:
+            for si, files in jpegs.items():
+                os.makedirs(os.path.join(out_dir, str(si)), exist_ok=True)
+                write_avi(os.path.join(out_dir, str(si), "video.avi"), files, width, height, fps)
     kept = []      # sheet: the fp32 frames, [frame index] -> (n, 3, H, W) (batched) or [sequence][frame index] -> (3, H, W)
 
     def write_sheet(frames5):
@@ -259,6 +285,8 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
                 frames.append(imgs)
                 if sheet:
                     kept.append(frame.detach().clone())
+                if video:
+                    encode(frame, 0)
                 if out_dir is not None:
                     from PIL import Image
                     for si in range(n):
@@ -269,6 +297,8 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
                 frame, obs = model.generate_next_interpolation_batch(obs, first_action, second_action, alphas)
         if sheet:
             write_sheet(torch.stack(kept, dim=1))
+        if video:
+            write_videos(int(start_observation.shape[-1]), int(start_observation.shape[-2]))
         return [np.stack([f[si] for f in frames], axis=0) for si in range(n)]
     with torch.no_grad():
         for si, alpha in enumerate(np.linspace(0.0, 1.0, steps + 1).tolist()):
@@ -281,6 +311,8 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
                 frames.append(img)
                 if sheet:
                     kept.append(frame.detach().clone())
+                if video:
+                    encode(frame[None], si)
                 if out_dir is not None:
                     from PIL import Image
                     os.makedirs(os.path.join(out_dir, str(si)), exist_ok=True)
@@ -291,6 +323,8 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
             sequences.append(np.stack(frames, axis=0))
     if sheet:
         write_sheet(torch.stack(kept).reshape(len(sequences), frames_count + 1, *kept[0].shape))
+    if video:
+        write_videos(int(start_observation.shape[-1]), int(start_observation.shape[-2]))
     return sequences
 
 
@@ -371,11 +405,15 @@ def main(argv=None) -> int:
     p = sub.add_parser("play"); p.add_argument("--config", required=True); p.add_argument("--actions", required=True, help="comma-separated, 1-based as typed in play.py")
     p.add_argument("--out", default="play_results"); p.add_argument("--sample", default="0:0", help="batch_index:observation_index of the first validation batch")
     p.add_argument("--device-frames", action="store_true", help="quantise the frames on the GPU (the same bytes)")
+    p.add_argument("--video", action="store_true", help="also write <out>/<sequence>/video.avi (Motion-JPEG, encoded on the GPU)")
+    p.add_argument("--fps", type=float, default=5, help="frames per second of --video (the reference's framerate: 5)"); p.add_argument("--video-quality", type=int, default=90)
     p = sub.add_parser("interpolate"); p.add_argument("--config", required=True); p.add_argument("--first", type=int, required=True); p.add_argument("--second", type=int, required=True)
     p.add_argument("--steps", type=int, default=6); p.add_argument("--frames", type=int, default=8); p.add_argument("--out", default=None)
     p.add_argument("--batched", action="store_true", help="advance all steps + 1 sequences as one batch per frame")
     p.add_argument("--device-frames", action="store_true", help="quantise the frames on the GPU (the same bytes); with --batched all sequences of a step in one launch")
     p.add_argument("--sheet", action="store_true", help="also write <out>/sheet.png: one row per interpolation value, composed on the GPU")
+    p.add_argument("--video", action="store_true", help="also write <out>/<i>/video.avi per interpolation value (Motion-JPEG, encoded on the GPU)")
+    p.add_argument("--fps", type=float, default=5, help="frames per second of --video (the reference's framerate: 5)"); p.add_argument("--video-quality", type=int, default=90)
     p = sub.add_parser("build-dataset"); p.add_argument("--config", required=True)
     p = sub.add_parser("evaluate-model"); p.add_argument("--config", required=True)
     p = sub.add_parser("evaluate"); p.add_argument("--config", required=True)
@@ -405,11 +443,13 @@ def main(argv=None) -> int:
     obs = _first_observations(datasets["validation"], config["evaluation"]["batching"]["batch_size"])
     if args.cmd == "play":
         b, o = (int(x) for x in args.sample.split(":"))
-        res = play_loop(model, obs[b, o].cuda(), [int(a) for a in args.actions.split(",") if a != ""], args.out, device_frames=args.device_frames)
+        res = play_loop(model, obs[b, o].cuda(), [int(a) for a in args.actions.split(",") if a != ""], args.out, device_frames=args.device_frames, video=args.video, fps=args.fps,
+                        video_quality=args.video_quality)
         logger.print(f"- {len(res['frames'])} frames written to {os.path.join(args.out, '0')}")
         return 0
     out = args.out or config["logging"]["interpolated_sequences"]
-    interpolate_loop(model, obs[0, 0].cuda(), args.first, args.second, args.steps, args.frames, out, batched=args.batched, device_frames=args.device_frames, sheet=args.sheet)
+    interpolate_loop(model, obs[0, 0].cuda(), args.first, args.second, args.steps, args.frames, out, batched=args.batched, device_frames=args.device_frames, sheet=args.sheet,
+                     video=args.video, fps=args.fps, video_quality=args.video_quality)
     logger.print(f"- {args.steps + 1} sequences written to {out}")
     return 0
 

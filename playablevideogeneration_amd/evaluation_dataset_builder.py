@@ -58,6 +58,8 @@ class EvaluationDatasetBuilder:
         self.action_variation_sampler = ZeroActionVariationSampler()
         self.temperature = config["training"]["gumbel_temperature_end"]
         self.batch_size = config["evaluation"]["batching"]["batch_size"]
+        from .video_writer import ComparisonVideos      # evaluation_dataset.save_videos: <output_directory>/videos/<sequence index>.avi
+        self.videos = ComparisonVideos(config, os.path.join(config["logging"].get("output_directory") or os.path.dirname(self.output_path), "videos"))
         self.device_quantise = bool(config["evaluation_dataset"].get("device_quantise", False))      # opt-in: pad, map and cast on the device (frame_pipeline.FrameWriter)
 
     def _batches(self):
@@ -108,6 +110,16 @@ class EvaluationDatasetBuilder:
                               f"(written as 0) in a batch of generated frames")
         return frames
 
+    def save_comparison(self, model, observations: torch.Tensor, generated_u8: torch.Tensor):
+        """evaluation_dataset.save_videos: the ground-truth frames (channels 0..2, quantised by the frame writer under the builder's own range rule) beside the generated bytes"""
+        if not self.videos.wanted():
+            return
+        from .frame_pipeline import MAP_IF_NEGATIVE, cached_writer
+        self.videos.lib = getattr(getattr(model, "module", model), "_lib", None)
+        truth = observations[:, :, :3].to(generated_u8.device, torch.float32).contiguous()
+        bs, T, _, H, W = truth.shape
+        self.videos.add(cached_writer(H, W, bs * T, self.videos.lib, truth.device)(truth, map=MAP_IF_NEGATIVE), generated_u8)
+
     def build(self, model, write: bool = True) -> List[EvaluationVideo]:
         all_videos: List[EvaluationVideo] = []
         was_training = model.training
@@ -119,13 +131,17 @@ class EvaluationDatasetBuilder:
                                 action_variation_sampler=self.action_variation_sampler, gumbel_temperature=self.temperature)
                 rec, selected_actions, sampled_dirs = results[0], results[5], results[11]
                 if self.device_quantise:
-                    all_videos.extend(self.bytes_to_videos(self.quantise_on_device(model, batch_tuple[0], rec).cpu().numpy(), selected_actions.cpu().numpy(),
-                                                           sampled_dirs.cpu().numpy()))
+                    frames = self.quantise_on_device(model, batch_tuple[0], rec)
+                    self.save_comparison(model, batch_tuple[0], frames)
+                    all_videos.extend(self.bytes_to_videos(frames.cpu().numpy(), selected_actions.cpu().numpy(), sampled_dirs.cpu().numpy()))
                     continue
                 first = batch_tuple[0][:, 0:1, 0:3].to(rec.device, rec.dtype)           # pad with the first ground-truth frame
                 rec = self.check_and_normalize_range(torch.cat([first, rec], dim=1))
                 images = np.moveaxis(rec.cpu().numpy(), 2, -1)
-                all_videos.extend(self.predictions_to_videos(images, selected_actions.cpu().numpy(), sampled_dirs.cpu().numpy()))
+                videos = self.predictions_to_videos(images, selected_actions.cpu().numpy(), sampled_dirs.cpu().numpy())
+                if self.videos.wanted():
+                    self.save_comparison(model, batch_tuple[0], torch.from_numpy(np.stack([v.frames for v in videos])).to(rec.device))
+                all_videos.extend(videos)
         model.train(was_training)
         if write:
             self.create_dataset(self.output_path, all_videos)

@@ -67,6 +67,8 @@ class ModelRollouts:
         self.lib = getattr(getattr(model, "module", model), "_lib", None)
         self.device = M.device(self.lib)
         self.last_stats = None
+        from .video_writer import ComparisonVideos      # evaluation_dataset.save_videos: <output_directory>/videos/<sequence index>.avi
+        self.videos = ComparisonVideos(config, os.path.join(config["logging"]["output_directory"], "videos"), self.lib)
 
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
@@ -103,7 +105,11 @@ class ModelRollouts:
                              action_variation_sampler=ZeroActionVariationSampler(), gumbel_temperature=self.temperature)
         rec, selected_actions, sampled_dirs = results[0], results[5], results[11]
         writer = cached_writer(H, W, bs * (int(rec.shape[1]) + 1), self.lib, dev)
-        generated = writer(rec, first=observations, map=MAP_IF_NEGATIVE, want_u8=False, want_f32=True)
+        if self.videos.wanted():      # the bytes too: reference | generated, joined and JPEG-encoded on the device (the reference's bytes are its [0, 1] values * 255, exactly)
+            generated_u8, generated = writer(rec, first=observations, map=MAP_IF_NEGATIVE, want_u8=True, want_f32=True)
+            self.videos.add((reference * 255.0).round().to(torch.uint8).permute(0, 1, 3, 4, 2), generated_u8)
+        else:
+            generated = writer(rec, first=observations, map=MAP_IF_NEGATIVE, want_u8=False, want_f32=True)
         self.last_stats = stats = writer.stats()
         if (stats["saturated"] or stats["nan"]) and self.logger is not None:
             self.logger.print(f"- Warning: {stats['saturated']} values outside the uint8 range after the range mapping (saturated to 0 / 255) and {stats['nan']} NaNs "
