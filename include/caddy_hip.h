@@ -526,6 +526,9 @@ int caddy_debug_set_perc_chunks(caddy_ctx* ctx, int n);
  * the ground truth's features for the sign of the L1 seed, also sum |f_rec - f_gt| for the level's loss; 0 = a stand-alone pass over both maps for every level.  Same gradients
  * bit for bit; the level sums are the same fp32 differences added in double in another order.  CADDY_PERC_FUSE_L1 sets the default of new contexts. */
 int caddy_debug_set_perc_fuse_l1(caddy_ctx* ctx, int on);
+/* tests (nothing is launched): plans the ground-truth VGG19 prefetch of a training forward pass with `trec` reconstructed frames (chunk count: caddy_debug_set_perc_chunks) and walks
+ * every (chunk, resolution level) the side stream would run.  out[0] = bytes of the side stream's scratch region, out[1] = bytes the largest walk needs, out[2] = chunks planned. */
+int caddy_debug_gt_scratch_check(caddy_ctx* ctx, int trec, long* out);
 long caddy_debug_s16_grad_count(caddy_ctx* ctx);
 int caddy_debug_set_pack_merged(caddy_ctx* ctx, int on);      /* tests: 0 = one (un)packing launch per layer and form instead of the job-table launch */
 int caddy_debug_dims(caddy_ctx* ctx, int i, int* nhwc4);
@@ -575,6 +578,8 @@ int caddy_k_conv_pick_bn(int cout);
 /* split 16-bit operand form of a layer's weights for the 16-bit-MFMA convolution (conv_hx.hip): seg < 0 forward, else dgrad of that segment */
 int caddy_k_hx_pick_bn(int cout);
 int caddy_k_hx_force_big(int v);      /* tests: 1 / 0 force / forbid the 8-wave 16x16x128 tile variant, -1 automatic */
+int caddy_k_conv_took_coresident(void);      /* 1: this thread's last split-operand 3x3 launch ran on the co-resident instance of the 16x16x128 tile */
+int caddy_k_vgg_beside(int v);        /* co-resident instance of that tile, a mask: bit 0 the VGG19 launches beside the forward pass, bit 1 those beside the BPTT replay, bit 2 every launch on the tile (tests); -1 = CADDY_VGG_BESIDE (default 1) */
 int caddy_k_hx_set_bg(int mask);   /* tests / A-B runs: which under-filled k_conv_hx tile variants read their weight fragments straight from global memory (conv_hx.hip, template
                                     * parameter BG; bit 0: 4x16x64, bit 1: 8x16x64, bit 2: 8x16x32 tiles; bit 3: also for workgroups that walk fewer than four 32-channel chunks); -1: the
                                     * CADDY_HX_BG environment variable, default 7 */

@@ -31,7 +31,8 @@ class ConvArgs(C.Structure):
                 ("stats", C.c_void_p), ("stats_ld", C.c_int), ("sat_flag", C.c_void_p), ("deterministic", C.c_int), ("direct_ok", C.c_int), ("lstm", C.c_void_p),
                 ("in_s16", C.c_int), ("out_s16", C.c_int), ("pool_s16", C.c_int), ("mask_s16", C.c_int), ("seed_s16", C.c_int),
                 ("avgpool", C.c_int), ("sat_out_next", C.c_int),      # S16 tensors (csrc/common.h): pre-split 16-bit operand pairs
-                ("l1_acc", C.c_void_p)]      # feature-L1 sum out of the seed epilogue (csrc/common.h)
+                ("l1_acc", C.c_void_p),      # feature-L1 sum out of the seed epilogue (csrc/common.h)
+                ("beside_chain", C.c_int)]      # the launch runs beside the model chain: co-resident tile instance (csrc/common.h)
 
 
 class LstmFuse(C.Structure):      # csrc/common.h: cell update applied by the slab reduce of a roll-out gate convolution (ConvArgs.lstm)

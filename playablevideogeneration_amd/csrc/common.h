@@ -135,6 +135,10 @@ struct ConvArgs {
     // launch adds sum |mask - seed_ref| over EVERY element of the map (ReLU mask open or not; fp32 differences, summed in double) to *l1_acc -- the two maps are in registers for
     // the sign of the seed, a stand-alone pass (perceptual.hip: k_feat_l1) would read both from HBM again.  One double atomic per workgroup; whole-K launches only.
     double* l1_acc;
+    // The launch runs while the model chain runs on another stream: 1 = beside the forward pass (VGG19: the ground-truth branch of vgg_gt_prefetch), 2 = beside the BPTT replay (the
+    // pipelined chunks behind the first one).  Where conv_hx_try would pick the 8-wave 16x16x128 tile it may then pick the co-resident instance (conv_hx_co.hip: one wave per SIMD,
+    // <= 256 registers), which leaves room on its CU for a workgroup of the chain; the results are bit-identical.  g_vgg_beside / CADDY_VGG_BESIDE say for which of the two.
+    int beside_chain;
 };
 int conv_avgpool_ok(const ConvArgs& a);      // (out / out_sn / out_ld need not be set yet)
 // gates = [i | f | o | g] x C pre-activations (convolutional_lstm_cell.py:92-101): c' = sigm(f) c + sigm(i) tanh(g), h' = sigm(o) tanh(c'), hb = h' * scale + shift (the cell's
@@ -214,6 +218,9 @@ int hx_pick_bn(int cout);
 // 8 g .. 8 g + 7 (g = 0 .. 3) of plane 0 of row `row`; plane 1 is 64 pieces further.  Fragment-major inside every 32-row block: [K half g >> 1][plane][lane = 32 (g & 1) + row & 31].
 template <int NPL> __host__ __device__ __forceinline__ long hx_wq_piece(int row, int g) { return ((long)((row >> 5) * 2 + (g >> 1)) * NPL) * 64 + (g & 1) * 32 + (row & 31); }
 extern int g_hx_big_override;
+extern thread_local int g_last_conv_co;      // conv_hx.hip: 1 = the last conv_hx_try of this thread launched the co-resident instance
+extern int g_vgg_beside; // conv_hx.hip: co-resident instance for ConvArgs.beside_chain launches (mask: -1 CADDY_VGG_BESIDE, bit 0 beside the forward pass, bit 1 beside the replay, bit 2 every 8-wave-tile launch)
+int conv_hx_co_launch(const ConvArgs& a, dim3 grid, int tx, int ty, int ep, int io, hipStream_t st);      // conv_hx_co.hip
 extern int g_hx_bg;      // conv_hx.hip: which under-filled tile variants take their weight fragments straight from global memory (bit mask; -1: CADDY_HX_BG or all)
 int conv_split_reduce_pool_launch(const float* scr, long stride, int splits, int ldc, int N, int H, int W, int C, float* out, long out_sn, int out_ld, const float* bias, int act,
                                   const float* res, long res_sn, int res_ld, hipStream_t st);      // slab reduce + avg_pool2d(2) (+ bias / residual / activation at the pooled size)

@@ -215,6 +215,7 @@ struct caddy_ctx {
     int perc_t0[PERC_MAX_CHUNKS + 1] = {};
     hipEvent_t perc_ev[PERC_MAX_CHUNKS] = {};
     bool perc_waited[PERC_MAX_CHUNKS] = {};
+    int vgg_beside = 0;              // the VGG19 launches being enqueued run beside the model chain: ConvArgs.beside_chain (1 forward pass, 2 tape replay; perceptual.hip)
     bool perc_pipelined = false;     // this loss_backward runs the chunks on the side stream beside the tape replay
     T4 gt_taps_c[PERC_MAX_CHUNKS][3][5]{};
     // time range [t0, t0 + len) of resolution level r handled with chunk k (false: nothing).  The full-resolution level follows the chunk table; the half- and quarter-resolution

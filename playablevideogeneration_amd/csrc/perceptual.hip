@@ -418,6 +418,7 @@ void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool ke
         a.src[0] = ConvSrc{x.d, x.sn, x.ld, x.C, round_up(x.C, CONV_BK), 0};
         a.nsrc = 1; a.N = x.N; a.H = x.H; a.W = x.W; a.KS = 3; a.wp = L.wp; a.Ktot = L.pd.Ktot; a.Cout = L.pd.Cout; a.Cout_pad = L.pd.Cout_pad;
         a.bias = L.bias; a.act = 2; a.out = out.d; a.out_sn = out.sn; a.out_ld = out.ld;
+        a.beside_chain = c->vgg_beside;
         a.precision = c->vgg_precision == PREC_F16X1 ? PREC_F16X1 : (c->vgg_precision == PREC_FP32 ? PREC_FP32 : (c->vgg_precision == PREC_BF16X3 ? PREC_BF16X3 : PREC_F16X3));
         // f16 range guard: real VGG19 weights on un-normalised inputs are where a forward activation could leave the f16 range.  A layer that reported it (caddy_f16_saturated) runs
         // on split bf16 from then on -- 8 + 8 mantissa bits, the full fp32 exponent range -- and only that layer (round 4 moved the whole context to exact fp32: 2.2 x slower)
@@ -463,10 +464,8 @@ void vgg_gt_prefetch(caddy_ctx* c, int Trec, int t_off) {
     c->perc_plan(Trec, c->training && !c->pretraining);
     c->gt_lo = (c->act.off + 255) & ~(size_t)255;
     T4 gimg[caddy_ctx::PERC_MAX_CHUNKS][3];
-    int kmax = 0;
     // (caddy_ctx::perc_range: the full-resolution level follows the chunk table, the half- and quarter-resolution levels are cut once)
     for (int k = 0; k < c->perc_nch; k++) {
-        if (c->perc_t0[k] - c->perc_t0[k + 1] > c->perc_t0[kmax] - c->perc_t0[kmax + 1]) kmax = k;
         for (int r = 0; r < 3; r++) {
             int t0, len;
             if (!c->perc_range(r, k, &t0, &len)) continue;
@@ -477,14 +476,17 @@ void vgg_gt_prefetch(caddy_ctx* c, int Trec, int t_off) {
         }
     }
     for (int r = 0; r < 3; r++) c->gt_img[r] = gimg[0][r];
-    {   // scratch for the non-tapped maps of the largest chunk at the largest resolution (allocation pattern of vgg_forward at r = 0)
+    {   // scratch for the non-tapped maps: the largest walk of vgg_forward over EVERY (chunk, level) the side stream will run -- with many short chunks the half of a smaller
+        // level that goes with chunk nch / 2 can need more than the longest full-resolution chunk and than the half that goes with chunk 0
         const size_t m0 = c->act.off;
         const bool was_dry = c->dry; c->dry = true;
         size_t end = m0;
-        for (int r = 0; r < 2; r++) {      // (the un-chunked half-resolution level can need more than a short full-resolution chunk)
+        for (int k = 0; k < c->perc_nch; k++) for (int r = 0; r < 3; r++) {
+            int t0, len;
+            if (!c->perc_range(r, k, &t0, &len)) continue;
             Branch G{};
             c->act.off = m0;
-            vgg_forward(c, gimg[r == 0 ? kmax : 0][r], G, c->gt_taps_c[r == 0 ? kmax : 0][r], false);
+            vgg_forward(c, gimg[k][r], G, c->gt_taps_c[k][r], false);
             if (c->act.off > end) end = c->act.off;
         }
         c->act.off = end;
@@ -499,6 +501,7 @@ void vgg_gt_prefetch(caddy_ctx* c, int Trec, int t_off) {
     if (!c->use_side || !c->side) return;
     hipStream_t main_st = c->stream, side = c->wgrad_stream();      // ordered after everything enqueued so far (the NHWC observations)
     c->stream = side;
+    c->vgg_beside = 1;                                       // (the model's forward pass runs on the main stream meanwhile)
     for (int k = 0; k < c->perc_nch; k++) {                  // (the order the loss call consumes them in: last time steps first)
         for (int r = 0; r < 3; r++) {
             int t0, len;
@@ -510,13 +513,38 @@ void vgg_gt_prefetch(caddy_ctx* c, int Trec, int t_off) {
             c->act.off = c->gt_scratch_off;                    // (host-side bump pointer only: the region is private to the side stream)
             Branch G{};
             vgg_forward(c, gi, G, c->gt_taps_c[k][r], false);
+            if (c->act.off > c->gt_scratch_end) { c->fail = true; set_error("internal: a ground-truth VGG19 walk passes the side stream's scratch region"); }
             for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) c->gt_taps_c[k][r][VS[i].tap].fmt = G.a[i].fmt;      // (a tapped map may be an S16 tensor)
             c->act.off = keep;
         }
     }
+    c->vgg_beside = 0;
     c->stream = main_st;
     hipEventRecord(c->gt_done, side);
     c->gt_prefetched = true;
+}
+
+int caddy_debug_gt_scratch_check(caddy_ctx* c, int trec, long* out) {
+    if (!c->cfg.perceptual) { set_error("caddy_debug_gt_scratch_check needs a context created with caddy_config.perceptual = 1"); return -2; }
+    const size_t keep = c->act.off, keep_high = c->act.high;
+    const bool was_dry = c->dry, was_training = c->training, was_pre = c->pretraining;
+    c->dry = true; c->training = true; c->pretraining = false;
+    vgg_gt_prefetch(c, trec, 1);
+    size_t need = 0;
+    for (int k = 0; k < c->perc_nch; k++) for (int r = 0; r < 3; r++) {
+        int t0, len;
+        if (!c->perc_range(r, k, &t0, &len)) continue;
+        const T4& t = c->gt_taps_c[k][r][0];
+        const T4 gi = valloc(c, t.N, t.H, t.W, 3);
+        c->act.off = c->gt_scratch_off;
+        Branch G{};
+        vgg_forward(c, gi, G, c->gt_taps_c[k][r], false);
+        if (c->act.off - c->gt_scratch_off > need) need = c->act.off - c->gt_scratch_off;
+    }
+    out[0] = (long)(c->gt_scratch_end - c->gt_scratch_off); out[1] = (long)need; out[2] = c->perc_nch;
+    c->act.off = keep; c->act.high = keep_high;
+    c->dry = was_dry; c->training = was_training; c->pretraining = was_pre;
+    return 0;
 }
 
 // Called from loss_backward after the L1 terms (which also wrote the resized ground-truth images gt_img[r]) and before the tape is replayed:
@@ -549,6 +577,7 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
     size_t side_base = mark_all;
     for (int k = 0; k < nch; k++) {
     const bool first_par = nch > 1 && k == 0 && (pipe || dry);      // (dry run: the same layout)
+    c->vgg_beside = (pipe && k >= 1) ? 2 : 0;                // the tape replay runs beside every chunk but the first (incl. the early halves of the smaller levels)
     for (int oi = 0; oi < 3; oi++) {
         const int r = first_par ? oi : (oi == 2 ? 0 : oi + 1);      // levels 1, 2, 0 -- the first chunk of the pipelined form 0 (main stream), 1, 2
         int t0, len;
@@ -620,6 +649,7 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
                 if (d.precision != PREC_FP32 && L.wqd[0]) d.wq = L.wqd[d.precision == PREC_BF16X1 ? 1 : 0];
                 d.out = in.g; d.out_sn = in.sn; d.out_ld = in.ld;
                 d.in_s16 = gzs[i] ? 1 : 0;
+                d.beside_chain = c->vgg_beside;
                 if (i == 0) d.accumulate = whole ? 1 : 0;                     // whole batch: += into d(rec_r), next to the L1 seed; a chunk: assigned to the gathered copy, added below
                 else if (!VS[i].pool_before) {                               // direct input a[i-1]: ReLU mask (+ L1 seed when a[i-1] is tapped) in the epilogue; the output IS gz_{i-1}
                     d.mask = in.d; d.mask_s16 = in.fmt;
@@ -661,6 +691,7 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
     }
     if (pipe) hipEventRecord(c->perc_ev[k], side);          // the seeds of the time steps [t0, t0 + len) are final (first chunk: its full-resolution level is ordered by the main stream itself)
     }
+    c->vgg_beside = 0;
     c->stream = st;
     if (par) {                                               // join: the tape replay reads d(rec_1), d(rec_2)
         hipEvent_t e = c->sev();
