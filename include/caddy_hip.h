@@ -355,6 +355,37 @@ int caddy_video_encode(caddy_ctx* ctx, const unsigned char* frames_u8, int n, un
 /* tests: the host copies of what the context built (each nullable): the two quantisation tables in natural order, luminance first (128 bytes); the header SOI .. SOS;
  * its length (623) */
 int caddy_video_tables_get(caddy_ctx* ctx, unsigned char* qtables128, unsigned char* header, int* header_bytes);                                                     /* utils/save_video_ffmpeg.py:172-198 */
+/* --- Device-side PNG writer (csrc/png.hip): the lossless files every driver writes (dataset folders NNNNN.png, the frames of play / interpolate, the evaluator's example sheets)
+ *     filtered, deflated and framed on the device, so that only the compressed bytes are left to copy.  A PNG context is an evaluation context of its own kind (no model, no
+ *     weights) for images of H x W; a call with more than max_frames images runs in chunks.  Destroy with caddy_ctx_destroy.  The files are not Pillow's bytes: the contract is
+ *     the PNG and deflate specifications -- any decoder returns exactly the input, and both checksums hold.  Each file is the 8-byte signature, IHDR (8 bits, colour type 2, no
+ *     interlace), one IDAT holding a zlib stream (header 0x78 0x01), IEND.  All arithmetic is integer and every combine is order independent (OR, XOR, integer sums), so a call
+ *     is reproducible bit for bit:
+ *       filter    bpp = 3, an all-zero row above row 0; filter_mode 0..4 applies that type (None, Sub, Up, Average, Paeth) to every row, CADDY_PNG_FILTER_ADAPTIVE computes all
+ *                 five and takes the smallest sum over the row of |byte as int8|, ties to the lower type.  The filtered stream is H rows of 1 + 3 W bytes (the type first).
+ *       deflate   the stream is cut at multiples of 16384 bytes and every block is compressed on its own: literals and distance-1 matches of length 3..258, taken greedily
+ *                 from the second byte of a run of equal bytes (runs restart at a block's first byte); the block goes out stored, fixed or dynamic, whichever is shortest in
+ *                 bytes (ties: stored, then fixed).  Dynamic: code lengths limited to 15 (literal / length, distance) and 7 (code-length code), canonical codes, at least two
+ *                 codes of non-zero length per tree as zlib does.  Every block but the last of an image is ended on a byte boundary by an empty stored block (3 zero bits, the
+ *                 padding, 00 00 FF FF) unless it ends on one already, so that the blocks' places are a prefix sum of their byte lengths.
+ *       checksums Adler-32 of the filtered stream from per-block sums; CRC-32 of the IDAT type and payload from the bytes as written, per piece by table and combined by
+ *                 multiplying with x^(8 len) mod P --- */
+#define CADDY_PNG_FILTER_ADAPTIVE 5
+#define CADDY_PNG_BLOCK 16384
+size_t caddy_png_workspace_bytes(int max_frames, int H, int W);
+/* filter_mode: 0..4 or CADDY_PNG_FILTER_ADAPTIVE.  NULL (caddy_last_error): sizes below 1, another filter_mode, or a geometry whose bound for one image,
+ * caddy_png_stream_bound(1, H, W), passes 2^31 - 1. */
+caddy_ctx* caddy_png_ctx_create(int max_frames, int H, int W, int filter_mode, void* workspace, size_t bytes);
+/* the output capacity no input of n images of H x W can exceed: n (63 + S + 5 ceil(S / 16384)) with S = H (1 + 3 W) -- a stored block is its bytes and 5 more (one byte of
+ * block header and padding, LEN, NLEN) and no block goes out longer than stored; 63 = signature 8 + IHDR 25 + IDAT length, type and CRC 12 + zlib header 2 + Adler-32 4 + IEND
+ * 12.  0 (caddy_last_error) for sizes or n below 1, or where one image's bound passes 2^31 - 1. */
+size_t caddy_png_stream_bound(int n, int H, int W);
+/* frames_u8 = (n, H, W, 3) uint8 interleaved RGB on the device (what caddy_frames_write and the sheets produce; any alignment); out_stream (device, out_capacity bytes) receives
+ * n complete files back to back; offsets (device, n + 1 words, 4-byte aligned) receives where each file starts and, last, the total length.  The caller copies the offsets and
+ * then out_stream[0, total) only.  Four launches per chunk of max_frames images on the context's stream; waits for nothing, allocates nothing.  Errors
+ * (-2, caddy_last_error): a context of another kind, null pointers, misaligned offsets, n < 1, out_capacity < caddy_png_stream_bound(n, H, W) (nothing is written: never a
+ * truncated stream), a bound of 2^32 bytes or more. */
+int caddy_png_encode(caddy_ctx* ctx, const unsigned char* frames_u8, int n, unsigned char* out_stream, size_t out_capacity, unsigned* offsets);
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

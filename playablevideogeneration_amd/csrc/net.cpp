@@ -9,6 +9,7 @@
 #include "frames.h"
 #include "sheets.h"
 #include "video.h"
+#include "png.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1684,6 +1685,7 @@ void caddy_ctx_destroy(caddy_ctx* c) {
     frames_free(c);
     sheets_free(c);
     video_free(c);
+    png_free(c);
     delete c;
 }
 int caddy_set_stream(caddy_ctx* c, void* s) { c->stream = (hipStream_t)s; return 0; }

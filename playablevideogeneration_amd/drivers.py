@@ -188,13 +188,35 @@ def _first_observations(dataset, batch_size: int) -> torch.Tensor:
     raise Exception("the validation split is empty")
 
 
+def device_frames_to_png(model, frames: torch.Tensor):
+    """(n, 3, H, W) in [-1, 1] -> ((n, H, W, 3) uint8 as device_frames_to_uint8 gives them, their n PNG files): quantised by the frame writer and filtered, deflated and
+    framed by the PNG writer (png_writer.PngEncoder, csrc/png.hip), all n frames in one encoder call"""
+    from .frame_pipeline import MAP_ALWAYS, cached_writer
+    from .png_writer import FILTER_ADAPTIVE, cached_png_encoder
+    n, _, H, W = frames.shape
+    lib = getattr(getattr(model, "module", model), "_lib", None)
+    u8 = cached_writer(H, W, n, lib, frames.device)(frames[None], map=MAP_ALWAYS)[0]
+    return u8.cpu().numpy(), cached_png_encoder(int(H), int(W), int(n), FILTER_ADAPTIVE, lib, frames.device)(u8)
+
+
+def _write_image(path: str, img, png=None):
+    """a frame to `path`: the ready file `png` (encoded on the device) where there is one, else PIL's encoding of the uint8 image"""
+    if png is not None:
+        with open(path, "wb") as f:
+            f.write(png)
+        return
+    from PIL import Image
+    Image.fromarray(img).save(path)
+
+
 def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], out_dir: Optional[str] = None, sequence_idx: int = 0, device_frames: bool = False,
-              video: bool = False, fps=5, video_quality: int = 90) -> Dict:
+              video: bool = False, fps=5, video_quality: int = 90, device_png: bool = False) -> Dict:
     """play.py:115-207 for ONE sequence: `actions` are what the user would type (1 .. actions_count; 0 = stop, implied at the end of the list).
     -> {"frames": uint8 (n + 1, H, W, 3), "actions": [...], "timestamps": [...]}; frames / metadata written under <out_dir>/<sequence_idx>/ when out_dir is given.
     device_frames: the frames are quantised on the device (device_frames_to_uint8) instead of frame_to_uint8 -- the same bytes.
     video: also <out_dir>/<sequence_idx>/video.avi (play.py:192 at `fps` frames per second): the frames the PNGs hold, quantised and JPEG-encoded on the device
-    (video_writer.save_video)."""
+    (video_writer.save_video).
+    device_png: the PNG files are encoded on the device too (device_frames_to_png; implies device_frames) -- files that decode to the same frames."""
     model.eval()
     kept = []      # video: the fp32 frames as generated
     seq_dir = None
@@ -208,7 +230,12 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
         model.start_inference()
         t0 = None
         for i in range(len(actions) + 1):
-            img = device_frames_to_uint8(model, frame[None])[0] if device_frames else frame_to_uint8(frame)
+            png = None
+            if device_png:
+                imgs, files = device_frames_to_png(model, frame[None])
+                img, png = imgs[0], files[0]
+            else:
+                img = device_frames_to_uint8(model, frame[None])[0] if device_frames else frame_to_uint8(frame)
             if t0 is None:
                 t0 = time.time()
                 stamps.append(0)
@@ -218,8 +245,7 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
             if video:
                 kept.append(frame.detach().clone())
             if seq_dir is not None:
-                from PIL import Image
-                Image.fromarray(img).save(os.path.join(seq_dir, f"{i}.png"))
+                _write_image(os.path.join(seq_dir, f"{i}.png"), img, png)
             if i == len(actions) or actions[i] == 0:
                 break
             a = int(actions[i]) - 1
@@ -238,13 +264,16 @@ def play_loop(model, start_observation: torch.Tensor, actions: Sequence[int], ou
 
 
 def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, second_action: int, steps: int, frames_count: int, out_dir: Optional[str] = None,
-                     batched: bool = False, device_frames: bool = False, sheet: bool = False, video: bool = False, fps=5, video_quality: int = 90) -> List[np.ndarray]:
+                     batched: bool = False, device_frames: bool = False, sheet: bool = False, video: bool = False, fps=5, video_quality: int = 90,
+                     device_png: bool = False) -> List[np.ndarray]:
     """interpolate.py:102-158: for each value in linspace(0, 1, steps + 1) one sequence of `frames_count` generate_next_interpolation calls from the same start.
     batched: all steps + 1 sequences advance as one batch per frame (one graph launch instead of steps + 1).
     device_frames: the frames are quantised on the device (device_frames_to_uint8), with `batched` all steps + 1 frames of a step in one launch -- the same bytes.
     sheet: also <out_dir>/sheet.png, one row per interpolation value, composed on the device from the frames as generated (example_sheets.ExampleSheets.strip).
     video: also <out_dir>/<i>/video.avi per interpolation value (interpolate.py:147 at `fps` frames per second), the frames the PNGs hold, quantised and JPEG-encoded on the
-    device (video_writer.JpegEncoder); with `batched` all values' frames of one step in one call -- the same files."""
+    device (video_writer.JpegEncoder); with `batched` all values' frames of one step in one call -- the same files.
+    device_png: the frames' PNG files and sheet.png are encoded on the device (png_writer.PngEncoder; implies device_frames); with `batched` all values' frames of one step
+    in one encoder call -- files that decode to the same frames."""
     model.eval()
     sequences = []
     jpegs: Dict[int, List[bytes]] = {}      # video: [sequence] -> the encoded frames
@@ -265,13 +294,12 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
     kept = []      # sheet: the fp32 frames, [frame index] -> (n, 3, H, W) (batched) or [sequence][frame index] -> (3, H, W)
 
     def write_sheet(frames5):
-        from PIL import Image
         from .example_sheets import MAP_ALWAYS, cached_sheets
         n, T = int(frames5.shape[0]), int(frames5.shape[1])
-        image = cached_sheets(n, T, getattr(getattr(model, "module", model), "_lib", None), frames5.device).strip(frames5, MAP_ALWAYS)
+        image = cached_sheets(n, T, getattr(getattr(model, "module", model), "_lib", None), frames5.device).strip(frames5, MAP_ALWAYS, device_png=device_png)
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
-            Image.fromarray(image).save(os.path.join(out_dir, "sheet.png"))
+            _write_image(os.path.join(out_dir, "sheet.png"), image, image if device_png else None)
     if batched:
         alphas = np.linspace(0.0, 1.0, steps + 1).tolist()
         n = len(alphas)
@@ -281,17 +309,21 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
             frame = obs[:, :3]
             frames = []
             for i in range(frames_count + 1):
-                imgs = list(device_frames_to_uint8(model, frame)) if device_frames else [frame_to_uint8(frame[si]) for si in range(n)]
+                pngs = [None] * n
+                if device_png:
+                    imgs, pngs = device_frames_to_png(model, frame)
+                    imgs = list(imgs)
+                else:
+                    imgs = list(device_frames_to_uint8(model, frame)) if device_frames else [frame_to_uint8(frame[si]) for si in range(n)]
                 frames.append(imgs)
                 if sheet:
                     kept.append(frame.detach().clone())
                 if video:
                     encode(frame, 0)
                 if out_dir is not None:
-                    from PIL import Image
                     for si in range(n):
                         os.makedirs(os.path.join(out_dir, str(si)), exist_ok=True)
-                        Image.fromarray(imgs[si]).save(os.path.join(out_dir, str(si), f"{i}.png"))
+                        _write_image(os.path.join(out_dir, str(si), f"{i}.png"), imgs[si], pngs[si])
                 if i == frames_count:
                     break
                 frame, obs = model.generate_next_interpolation_batch(obs, first_action, second_action, alphas)
@@ -307,16 +339,20 @@ def interpolate_loop(model, start_observation: torch.Tensor, first_action: int, 
             frame = obs[:3]
             frames = []
             for i in range(frames_count + 1):
-                img = device_frames_to_uint8(model, frame[None])[0] if device_frames else frame_to_uint8(frame)
+                png = None
+                if device_png:
+                    imgs, files = device_frames_to_png(model, frame[None])
+                    img, png = imgs[0], files[0]
+                else:
+                    img = device_frames_to_uint8(model, frame[None])[0] if device_frames else frame_to_uint8(frame)
                 frames.append(img)
                 if sheet:
                     kept.append(frame.detach().clone())
                 if video:
                     encode(frame[None], si)
                 if out_dir is not None:
-                    from PIL import Image
                     os.makedirs(os.path.join(out_dir, str(si)), exist_ok=True)
-                    Image.fromarray(img).save(os.path.join(out_dir, str(si), f"{i}.png"))
+                    _write_image(os.path.join(out_dir, str(si), f"{i}.png"), img, png)
                 if i == frames_count:
                     break
                 frame, obs = model.generate_next_interpolation(obs, first_action, second_action, alpha)
@@ -405,12 +441,14 @@ def main(argv=None) -> int:
     p = sub.add_parser("play"); p.add_argument("--config", required=True); p.add_argument("--actions", required=True, help="comma-separated, 1-based as typed in play.py")
     p.add_argument("--out", default="play_results"); p.add_argument("--sample", default="0:0", help="batch_index:observation_index of the first validation batch")
     p.add_argument("--device-frames", action="store_true", help="quantise the frames on the GPU (the same bytes)")
+    p.add_argument("--device-png", action="store_true", help="quantise the frames and encode their PNG files on the GPU (files that decode to the same frames)")
     p.add_argument("--video", action="store_true", help="also write <out>/<sequence>/video.avi (Motion-JPEG, encoded on the GPU)")
     p.add_argument("--fps", type=float, default=5, help="frames per second of --video (the reference's framerate: 5)"); p.add_argument("--video-quality", type=int, default=90)
     p = sub.add_parser("interpolate"); p.add_argument("--config", required=True); p.add_argument("--first", type=int, required=True); p.add_argument("--second", type=int, required=True)
     p.add_argument("--steps", type=int, default=6); p.add_argument("--frames", type=int, default=8); p.add_argument("--out", default=None)
     p.add_argument("--batched", action="store_true", help="advance all steps + 1 sequences as one batch per frame")
     p.add_argument("--device-frames", action="store_true", help="quantise the frames on the GPU (the same bytes); with --batched all sequences of a step in one launch")
+    p.add_argument("--device-png", action="store_true", help="quantise the frames and encode their PNG files (and sheet.png) on the GPU; with --batched all sequences of a step in one call")
     p.add_argument("--sheet", action="store_true", help="also write <out>/sheet.png: one row per interpolation value, composed on the GPU")
     p.add_argument("--video", action="store_true", help="also write <out>/<i>/video.avi per interpolation value (Motion-JPEG, encoded on the GPU)")
     p.add_argument("--fps", type=float, default=5, help="frames per second of --video (the reference's framerate: 5)"); p.add_argument("--video-quality", type=int, default=90)
@@ -444,12 +482,12 @@ def main(argv=None) -> int:
     if args.cmd == "play":
         b, o = (int(x) for x in args.sample.split(":"))
         res = play_loop(model, obs[b, o].cuda(), [int(a) for a in args.actions.split(",") if a != ""], args.out, device_frames=args.device_frames, video=args.video, fps=args.fps,
-                        video_quality=args.video_quality)
+                        video_quality=args.video_quality, device_png=args.device_png)
         logger.print(f"- {len(res['frames'])} frames written to {os.path.join(args.out, '0')}")
         return 0
     out = args.out or config["logging"]["interpolated_sequences"]
     interpolate_loop(model, obs[0, 0].cuda(), args.first, args.second, args.steps, args.frames, out, batched=args.batched, device_frames=args.device_frames, sheet=args.sheet,
-                     video=args.video, fps=args.fps, video_quality=args.video_quality)
+                     video=args.video, fps=args.fps, video_quality=args.video_quality, device_png=args.device_png)
     logger.print(f"- {args.steps + 1} sequences written to {out}")
     return 0
 

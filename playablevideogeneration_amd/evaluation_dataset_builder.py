@@ -9,7 +9,9 @@ padded with the first ground-truth frame, mapped from [-1, 1] to [0, 1] when its
 the reference's dataset format (dataset/video.py:95-156): `NNNNN.png` frames + `actions.pkl`, `rewards.pkl`, `metadata.pkl`, `dones.pkl`.
 By default nothing but the forward runs on the GPU; the forward is the same `caddy_forward_full` the training step uses.  With `evaluation_dataset.device_quantise: true`
 the padding, the range mapping and the truncating cast run on the device too (frame_pipeline.FrameWriter, csrc/frames.hip) and only uint8 frames cross to the host: the same
-bytes, a quarter of the traffic.
+bytes, a quarter of the traffic.  With `evaluation_dataset.device_png: true` (which implies device_quantise) the frames are also filtered, deflated and framed as PNG
+files on the device (png_writer.PngEncoder, csrc/png.hip): only the compressed files cross to the host, and `EvaluationVideo.save` writes them as they are -- files that
+decode to the same arrays.
 """
 import os
 import pickle
@@ -23,7 +25,8 @@ from .batching import collate_fn_for
 
 
 class EvaluationVideo:
-    """One generated sequence in the reference's on-disk layout (dataset/video.py: frames, actions, rewards, metadata, dones)."""
+    """One generated sequence in the reference's on-disk layout (dataset/video.py: frames, actions, rewards, metadata, dones).  `frames`: (T, H, W, 3) uint8, or T ready
+    PNG files (bytes) as the device-side PNG writer produced them."""
 
     def __init__(self, frames: np.ndarray, actions: List, rewards: List, metadata: List, dones: List):
         n = len(frames)
@@ -40,7 +43,13 @@ class EvaluationVideo:
                 pickle.dump(obj, f)
         from PIL import Image
         for i, fr in enumerate(self.frames):
-            Image.fromarray(fr).save(os.path.join(path, f"{i:05d}.{extension}"))
+            if isinstance(fr, (bytes, bytearray)):      # a ready file
+                if extension != "png":
+                    raise Exception(f"ready PNG files cannot be saved as '{extension}'")
+                with open(os.path.join(path, f"{i:05d}.{extension}"), "wb") as f:
+                    f.write(fr)
+            else:
+                Image.fromarray(fr).save(os.path.join(path, f"{i:05d}.{extension}"))
 
 
 def sequence_metadata(actions: np.ndarray, encoded_mus: np.ndarray) -> List:
@@ -60,7 +69,8 @@ class EvaluationDatasetBuilder:
         self.batch_size = config["evaluation"]["batching"]["batch_size"]
         from .video_writer import ComparisonVideos      # evaluation_dataset.save_videos: <output_directory>/videos/<sequence index>.avi
         self.videos = ComparisonVideos(config, os.path.join(config["logging"].get("output_directory") or os.path.dirname(self.output_path), "videos"))
-        self.device_quantise = bool(config["evaluation_dataset"].get("device_quantise", False))      # opt-in: pad, map and cast on the device (frame_pipeline.FrameWriter)
+        self.device_png = bool(config["evaluation_dataset"].get("device_png", False))                # opt-in: the PNG files too (png_writer.PngEncoder); implies device_quantise
+        self.device_quantise = self.device_png or bool(config["evaluation_dataset"].get("device_quantise", False))      # opt-in: pad, map and cast on the device (frame_pipeline.FrameWriter)
 
     def _batches(self):
         """DataLoader(dataset, batch_size, shuffle=False, collate_fn=single_batch_elements_collate_fn) for datasets of BatchElements
@@ -86,8 +96,8 @@ class EvaluationDatasetBuilder:
         return self.bytes_to_videos((images * 255).astype(np.uint8), actions, encoded_mus)
 
     def bytes_to_videos(self, images: np.ndarray, actions: np.ndarray, encoded_mus: np.ndarray) -> List[EvaluationVideo]:
-        """predictions_to_videos behind its cast: (bs, T, H, W, C) uint8 images"""
-        bs, T = images.shape[:2]
+        """predictions_to_videos behind its cast: (bs, T, H, W, C) uint8 images, or [bs][T] ready PNG files"""
+        bs, T = len(images), len(images[0])
         if actions.shape[0] != bs:
             raise Exception(f"Images have batch size {bs} but actions have batch size {actions.shape[0]}")
         if actions.shape[1] != T - 1:
@@ -133,7 +143,14 @@ class EvaluationDatasetBuilder:
                 if self.device_quantise:
                     frames = self.quantise_on_device(model, batch_tuple[0], rec)
                     self.save_comparison(model, batch_tuple[0], frames)
-                    all_videos.extend(self.bytes_to_videos(frames.cpu().numpy(), selected_actions.cpu().numpy(), sampled_dirs.cpu().numpy()))
+                    if self.device_png:      # only the compressed files cross to the host
+                        from .png_writer import encode_pngs
+                        bs, T = int(frames.shape[0]), int(frames.shape[1])
+                        files = encode_pngs(model, frames.reshape(bs * T, *frames.shape[2:]))
+                        images = [files[b * T:(b + 1) * T] for b in range(bs)]
+                    else:
+                        images = frames.cpu().numpy()
+                    all_videos.extend(self.bytes_to_videos(images, selected_actions.cpu().numpy(), sampled_dirs.cpu().numpy()))
                     continue
                 first = batch_tuple[0][:, 0:1, 0:3].to(rec.device, rec.dtype)           # pad with the first ground-truth frame
                 rec = self.check_and_normalize_range(torch.cat([first, rec], dim=1))

@@ -64,6 +64,7 @@ class Evaluator:
         self.batch_size = ev.get("batching", {}).get("batch_size", 8)
         self.max_evaluation_batches = ev.get("max_evaluation_batches", None)
         self.save_examples = bool(ev.get("save_examples", False))
+        self.device_png = bool(ev.get("device_png", False))      # the example sheets leave the device as PNG files (png_writer.PngEncoder), not as raw images
         self.action_sampler = action_sampler
         self.best_action_mappings: Optional[Dict[int, int]] = None
 
@@ -109,9 +110,14 @@ class Evaluator:
         bias = float(self.config.get("training", {}).get("motion_weights_bias", 0.0))
         lib = getattr(getattr(model, "module", model), "_lib", None)
         written = []
-        for key, image in evaluation_sheets(observations.to(multiresolution_reconstructions[0].device), list(multiresolution_reconstructions), bias, lib, say).items():
+        sheets = evaluation_sheets(observations.to(multiresolution_reconstructions[0].device), list(multiresolution_reconstructions), bias, lib, say, device_png=self.device_png)
+        for key, image in sheets.items():
             written.append(os.path.join(directory, f"{step:09}_{key}.png"))
-            Image.fromarray(image).save(written[-1])
+            if self.device_png:      # a ready file, encoded on the device
+                with open(written[-1], "wb") as f:
+                    f.write(image)
+            else:
+                Image.fromarray(image).save(written[-1])
         return written
 
     def evaluate(self, model, step: int) -> Dict[str, float]:

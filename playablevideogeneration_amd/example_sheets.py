@@ -60,7 +60,8 @@ class ExampleSheets(M._EvalContext):
     """A SHEETS context for sheets of at most `max_rows` rows of `max_cols` cells.  `colour_table`: (256, 3) float64, by default matplotlib's viridis (None without matplotlib:
     the motion-weighted sheet is then not available).
     `examples(obs, rec, weighted=False, bias=0.0)` -> (2 min(B, 30) (h + 2) + 2, T (w + 2) + 2, 3) uint8 numpy; `strip(frames, map)` -> (n (h + 2) + 2, T (w + 2) + 2, 3);
-    `stats()` -> {"mapped_gt", "mapped_rec", "saturated", "nan", "mask_invalid"} of the last sheet."""
+    `stats()` -> {"mapped_gt", "mapped_rec", "saturated", "nan", "mask_invalid"} of the last sheet.  With `device_png=True` both return the sheet as a complete PNG file
+    (bytes) encoded on the device (png_writer.PngEncoder): only the compressed bytes are copied."""
 
     def __init__(self, max_rows: int = 2 * MAX_SEQUENCES, max_cols: int = 64, lib=None, device=None, colour_table=None):
         super().__init__(0, 0, max_rows, lib, device)
@@ -76,7 +77,13 @@ class ExampleSheets(M._EvalContext):
     def _image(self, rows, T, h, w):
         return torch.empty(*sheet_shape(rows, T, h, w), dtype=torch.uint8, device=self.device)
 
-    def examples(self, obs: torch.Tensor, rec: torch.Tensor, weighted: bool = False, bias: float = 0.0) -> np.ndarray:
+    def _result(self, out: torch.Tensor, device_png: bool):
+        if not device_png:
+            return out.cpu().numpy()
+        from .png_writer import FILTER_ADAPTIVE, cached_png_encoder
+        return cached_png_encoder(int(out.shape[0]), int(out.shape[1]), 1, FILTER_ADAPTIVE, self.lib, self.device)(out[None])[0]
+
+    def examples(self, obs: torch.Tensor, rec: torch.Tensor, weighted: bool = False, bias: float = 0.0, device_png: bool = False):
         if obs.dim() != 5 or obs.dtype != torch.float32 or rec.dim() != 5 or rec.dtype != torch.float32 or rec.shape[2] != 3 or rec.shape[0] != obs.shape[0]:
             raise ValueError(f"expected (B, T, 3 S, H, W) observations and (B, Trec, 3, h, w) frames, both fp32, got {tuple(obs.shape)} {obs.dtype} and {tuple(rec.shape)} {rec.dtype}")
         if weighted and self.lut is None:
@@ -88,9 +95,9 @@ class ExampleSheets(M._EvalContext):
         self._stream()
         self._check(self.lib.caddy_sheet_examples(self.ctx, obs.data_ptr(), B, T, Cn, H, W, rec.data_ptr(), Trec, h, w, int(bool(weighted)), float(bias),
                                                   self.lut.data_ptr() if self.lut is not None else None, out.data_ptr()))
-        return out.cpu().numpy()
+        return self._result(out, device_png)
 
-    def strip(self, frames: torch.Tensor, map: int = MAP_ALWAYS) -> np.ndarray:
+    def strip(self, frames: torch.Tensor, map: int = MAP_ALWAYS, device_png: bool = False):
         if frames.dim() != 5 or frames.dtype != torch.float32 or frames.shape[2] != 3:
             raise ValueError(f"expected (n, T, 3, h, w) fp32 frames, got {tuple(frames.shape)} {frames.dtype}")
         frames = frames.detach().to(self.device).contiguous()
@@ -98,7 +105,7 @@ class ExampleSheets(M._EvalContext):
         out = self._image(n, T, h, w)
         self._stream()
         self._check(self.lib.caddy_sheet_strip(self.ctx, frames.data_ptr(), n, T, h, w, int(map), out.data_ptr()))
-        return out.cpu().numpy()
+        return self._result(out, device_png)
 
     def stats(self):
         """counted on the device for the last sheet; waits for the stream"""
@@ -118,8 +125,8 @@ def cached_sheets(rows: int, cols: int, lib=None, device=None) -> ExampleSheets:
     return M._cached(key, None, lambda: ExampleSheets(room_r, room_c, lib, device), lambda es: es.max_rows < rows or es.max_cols < cols)
 
 
-def evaluation_sheets(observations: torch.Tensor, multiresolution_reconstructions, bias: float, lib=None, log=None):
-    """the sheets of evaluator.py:128-138 for one forward pass -> {log key: uint8 image}: "observations_r{i}" for every resolution and "motion_weighted_observations_" on the
+def evaluation_sheets(observations: torch.Tensor, multiresolution_reconstructions, bias: float, lib=None, log=None, device_png: bool = False):
+    """the sheets of evaluator.py:128-138 for one forward pass -> {log key: uint8 image, or with device_png its PNG file encoded on the device}: "observations_r{i}" for every resolution and "motion_weighted_observations_" on the
     full-resolution reconstruction (multiresolution_reconstructions[0]).  The weighted sheet is left out, with a logged line, without matplotlib or when the mask holds a NaN
     or a negative value (the reference's assert)."""
     say = log if log is not None else _log.warning
@@ -127,11 +134,11 @@ def evaluation_sheets(observations: torch.Tensor, multiresolution_reconstruction
     sheets = cached_sheets(2 * min(int(observations.shape[0]), MAX_SEQUENCES), int(observations.shape[1]), lib, first.device)
     out = {}
     for i, rec in enumerate(multiresolution_reconstructions):
-        out[f"observations_r{i}"] = sheets.examples(observations, rec)
+        out[f"observations_r{i}"] = sheets.examples(observations, rec, device_png=device_png)
     if sheets.lut is None:
         say("motion-weighted example sheet not written: matplotlib is not available")
         return out
-    image = sheets.examples(observations, first, weighted=True, bias=bias)
+    image = sheets.examples(observations, first, weighted=True, bias=bias, device_png=device_png)
     if sheets.stats()["mask_invalid"]:
         say("motion-weighted example sheet not written: the motion weight mask holds a NaN or a negative value")
         return out
