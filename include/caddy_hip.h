@@ -386,6 +386,43 @@ size_t caddy_png_stream_bound(int n, int H, int W);
  * (-2, caddy_last_error): a context of another kind, null pointers, misaligned offsets, n < 1, out_capacity < caddy_png_stream_bound(n, H, W) (nothing is written: never a
  * truncated stream), a bound of 2^32 bytes or more. */
 int caddy_png_encode(caddy_ctx* ctx, const unsigned char* frames_u8, int n, unsigned char* out_stream, size_t out_capacity, unsigned* offsets);
+/* --- Device-side PNG reader (csrc/png_read.hip): the files of a frame folder (NNNNN.png, dataset/video.py: Image.open per frame in a DataLoader worker) parsed, inflated and
+ *     unfiltered on the device, so that the compressed bytes cross to the device instead of raw uint8 frames, and the frames appear where caddy_frames_observations reads them.
+ *     A PNG-read context is an evaluation context of its own kind (no model, no weights) for images of H x W; a call with more than max_frames images runs in chunks.  Destroy
+ *     with caddy_ctx_destroy.  The contract is the bytes: frames_u8 is what Pillow decodes, and a zlib stream is accepted exactly where zlib's inflate accepts it:
+ *       parse     signature; IHDR first, 13 bytes, 8 bits, colour type 2, compression 0, filter 0, interlace 0, width and height those of the context; chunks walked to IEND;
+ *                 CRC-32 of IHDR, every IDAT and IEND verified (ancillary CRCs are not, as in Pillow); the IDAT payloads, any number of any length, gathered; ancillary chunks and
+ *                 PLTE skipped, any other critical chunk refused
+ *       inflate   zlib header (CM 8, CINFO <= 7, FCHECK, no FDICT); stored (LEN against NLEN), fixed and dynamic blocks (HLIT <= 286, HDIST <= 30, repeats 16 / 17 / 18 across
+ *                 the literal / distance boundary, codes to 15 bits), matches 3..258 at 1..32768 also overlapping; refused: over-subscribed sets, incomplete sets other than one
+ *                 single code of length 1, a missing end-of-block code, symbols 286 / 287, distance codes 30 / 31, a distance beyond the bytes produced, block type 3; the
+ *                 Adler-32 verified; bytes behind it ignored
+ *       unfilter  exactly H (1 + 3 W) bytes, every type byte 0..4; None, Sub, Up, Average, Paeth with bpp = 3 and a zero row above row 0
+ *     Safety: every read of the blob is bounded by the end of that file (clamped to offsets[n]; past it zero bits, CADDY_PNG_TRUNCATED), every write by the image's own frame and
+ *     workspace slice; a bad file costs its own status word, its frame is zero-filled and the other images decode normally.
+ *     The capacity for one image's IDAT bytes is S + ((S + 7) >> 3) + ((S + 63) >> 6) + 11, S = H (1 + 3 W): zlib's deflateBound for parameters other than its defaults
+ *     (Pillow sets memLevel 9) and the 6 bytes of the zlib wrapper, which holds Pillow's files at every level and, being above S + 5 ceil(S / 16384) + 6 for every S, what
+ *     caddy_png_encode writes; more gives CADDY_PNG_TOO_LARGE --- */
+#define CADDY_PNG_OK 0
+#define CADDY_PNG_NOT_PNG 1          /* no signature, or no IHDR of 13 bytes behind it */
+#define CADDY_PNG_TRUNCATED 2        /* the file ends inside the signature, a chunk or the zlib stream, or before IEND */
+#define CADDY_PNG_BAD_CRC 3          /* IHDR, an IDAT or IEND */
+#define CADDY_PNG_UNSUPPORTED 4      /* bit depth, colour type, interlace, compression or filter method, an unknown critical chunk */
+#define CADDY_PNG_GEOMETRY 5         /* width or height other than the context's */
+#define CADDY_PNG_BAD_DEFLATE 6      /* the zlib header or a block is one zlib refuses */
+#define CADDY_PNG_BAD_ADLER 7
+#define CADDY_PNG_BAD_LENGTH 8       /* the inflated length is not H (1 + 3 W) */
+#define CADDY_PNG_BAD_FILTER 9       /* a row's type byte above 4 */
+#define CADDY_PNG_TOO_LARGE 10       /* more IDAT bytes than the context's capacity for one image */
+/* 0 (caddy_last_error): the geometry limits of caddy_png_ctx_create */
+size_t caddy_png_read_workspace_bytes(int max_frames, int H, int W);
+caddy_ctx* caddy_png_read_ctx_create(int max_frames, int H, int W, void* workspace, size_t bytes);
+/* files (device): n files back to back; offsets (device, n + 1 words, 4-byte aligned): where each starts and, last, the total length -- what caddy_png_encode leaves, so its
+ * output decodes without touching the host.  frames_u8 (device, (n, H, W, 3) uint8, any alignment) and status (device, n words, 4-byte aligned, CADDY_PNG_*) receive the result.
+ * Offsets that are not monotonic or pass offsets[n] give that image an empty or shortened file (CADDY_PNG_TRUNCATED / CADDY_PNG_NOT_PNG), never a read outside
+ * files[0, offsets[n]).  One launch per chunk of max_frames images on the context's stream; waits for nothing, allocates nothing.  Returns 0 when it
+ * ran -- the verdicts are in status.  Errors (-2, caddy_last_error; nothing is launched): a context of another kind, null pointers, misaligned offsets or status, n < 1. */
+int caddy_png_decode(caddy_ctx* ctx, const unsigned char* files, const unsigned* offsets, int n, unsigned char* frames_u8, int* status);     /* dataset/video.py:136-157 */
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

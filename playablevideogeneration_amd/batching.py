@@ -6,6 +6,8 @@
     normalisation       dataset/transforms.py:90-107       (ToTensor + Normalize(0.5, 0.5): uint8 [0, 255] -> fp32 [-1, 1])
     device transforms   (opt-in) RawBatchElement / RawBatch: the distinct uint8 frames of a batch plus the (bs, T, S) list of which frame fills which
                         slot; `RawBatch.to_tuple()` runs crop, resize, normalisation and stacking as one HIP kernel (frame_pipeline.py, csrc/frames.hip)
+    device decode       (opt-in) CodedBatchElement / CodedBatch: the same, with every distinct frame as the bytes of its PNG file; `CodedBatch.decode()` inflates and
+                        unfilters them on the device (png_reader.py, csrc/png_read.hip) into the frames a RawBatch holds
 
 The tensor contract lives here; the reader of the reference's on-disk format (PNG folders + pickles, dataset/video.py) and the sample
 grid over videos is `playablevideogeneration_amd.video_dataset`.  `Batch.to_tuple()` moves
@@ -116,13 +118,30 @@ class RawBatch:
         self.actions, self.rewards, self.dones = actions, rewards, dones
         self.video, self.initial_frames = videos, initial_frames
 
+    @property
+    def n_frames(self) -> int:
+        return int(self.frames.shape[0])
+
+    @property
+    def frame_hw(self) -> Tuple[int, int]:
+        return int(self.frames.shape[1]), int(self.frames.shape[2])
+
+    def staged(self) -> Tuple:
+        """the tensors that carry the frames to the device"""
+        return (self.frames,)
+
+    def device_frames(self, staged: Tuple, lib=None, device=None) -> torch.Tensor:
+        """(F, h, w, 3) uint8 from the copies of `staged()` on the device, on the current stream"""
+        return staged[0]
+
     def observations(self, frames: torch.Tensor = None, slot_src: torch.Tensor = None, lib=None, device=None) -> torch.Tensor:
         """(bs, T, 3 S, H, W) fp32 on the pipeline's device, from this batch's frames (or their staged copies) on the current stream"""
         from .frame_pipeline import cached_pipeline, validate_slots
-        validate_slots(self.slot_src, int(self.frames.shape[0]))
-        frames = self.frames if frames is None else frames
+        validate_slots(self.slot_src, self.n_frames)
+        frames = self.device_frames(self.staged(), lib, device) if frames is None else frames
         slot_src = self.slot_src if slot_src is None else slot_src
-        pipe = cached_pipeline(int(self.frames.shape[1]), int(self.frames.shape[2]), self.spec.crop, self.spec.size, self.spec.mode, int(self.frames.shape[0]), lib, device)
+        h, w = self.frame_hw
+        pipe = cached_pipeline(h, w, self.spec.crop, self.spec.size, self.spec.mode, self.n_frames, lib, device)
         bs, T, S = self.slot_src.shape
         return pipe(frames, slot_src).view(bs, T, 3 * S, pipe.H, pipe.W)
 
@@ -159,8 +178,84 @@ def raw_batch_elements_collate_fn(batch: List[RawBatchElement]) -> RawBatch:
                     [el.video for el in batch], [el.initial_frame_index for el in batch])
 
 
+class CodedBatchElement(RawBatchElement):
+    """A RawBatchElement whose `frames` are still files (video_dataset.raw_frame_spec(decode="device")): uint8 arrays of the bytes of each distinct frame's PNG,
+    all of `frame_hw` = (h, w); `sources[k]` = (video path, frame index) of frame k, for messages."""
+
+    def __init__(self, frames, frame_hw, sources, stack_indices, actions, rewards, dones, spec, video=None, initial_frame_index: int = 0):
+        super().__init__(frames, stack_indices, actions, rewards, dones, spec, video, initial_frame_index)
+        self.frame_hw, self.sources = tuple(frame_hw), list(sources)
+
+
+class CodedBatch(RawBatch):
+    """A RawBatch before its frames are decoded: `blob` uint8, the PNG files of the distinct frames back to back, `offsets` int32 (F + 1), `frame_hw` their common
+    (h, w).  `decode()` gives the RawBatch with `frames` on the device (png_reader.PngDecoder: the compressed bytes cross the bus, the device inflates and unfilters);
+    `observations()` / `to_tuple()` decode first and return what RawBatch returns, bit for bit.  A file the decoder refuses raises, naming its video and frame."""
+
+    def __init__(self, blob: torch.Tensor, offsets: torch.Tensor, frame_hw, sources, slot_src: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor, dones: torch.Tensor, spec,
+                 videos=None, initial_frames=None):
+        super().__init__(None, slot_src, actions, rewards, dones, spec, videos, initial_frames)
+        self.blob, self.offsets, self.sources = blob, offsets, list(sources)
+        self._hw = (int(frame_hw[0]), int(frame_hw[1]))
+
+    @property
+    def n_frames(self) -> int:
+        return int(self.offsets.numel()) - 1
+
+    @property
+    def frame_hw(self) -> Tuple[int, int]:
+        return self._hw
+
+    def staged(self) -> Tuple:
+        return (self.blob, self.offsets)
+
+    def device_frames(self, staged: Tuple, lib=None, device=None) -> torch.Tensor:
+        from . import metrics as M
+        from .png_reader import cached_png_decoder, status_error
+        device = torch.device(device) if device is not None else M.device(lib)
+        blob, offsets = (t.to(device, non_blocking=True) for t in staged)
+        frames, status = cached_png_decoder(self._hw[0], self._hw[1], self.n_frames, lib, device).decode_stream(blob, offsets)
+        error = status_error(status.cpu().tolist(), [f"{path} frame {index}" for path, index in self.sources])
+        if error is not None:
+            raise error
+        return frames
+
+    def decode(self, lib=None, device=None) -> RawBatch:
+        """the RawBatch of this batch, its frames decoded on the device (on the current stream)"""
+        return RawBatch(self.device_frames(self.staged(), lib, device), self.slot_src, self.actions, self.rewards, self.dones, self.spec, self.video, self.initial_frames)
+
+    def pin_memory(self):
+        self.blob, self.offsets, self.slot_src = self.blob.pin_memory(), self.offsets.pin_memory(), self.slot_src.pin_memory()
+        self.actions, self.rewards, self.dones = self.actions.pin_memory(), self.rewards.pin_memory(), self.dones.pin_memory()
+        return self
+
+
+def coded_batch_elements_collate_fn(batch: List[CodedBatchElement]) -> CodedBatch:
+    """the collate function of CodedBatchElements: the files are concatenated once each, the stack indices shifted by the frames in front of their element"""
+    import numpy as np
+    hw = batch[0].frame_hw
+    files, sources, slots = [], [], []
+    for el in batch:
+        if el.frame_hw != hw:
+            raise Exception(f"frames of different sizes in one batch: {hw} and {el.frame_hw} ({el.sources[0][0]}; such datasets keep the host transform)")
+        slots.append(torch.tensor(el.stack_indices, dtype=torch.int32) + len(files))
+        files.extend(el.frames)
+        sources.extend(el.sources)
+    offsets = np.zeros(len(files) + 1, np.int64)
+    np.cumsum([f.size for f in files], out=offsets[1:])
+    if offsets[-1] >= 1 << 31:
+        raise Exception(f"the files of one batch hold {int(offsets[-1])} bytes: more than the 32-bit offsets of the device decoder take")
+    actions = torch.stack([torch.tensor(el.actions, dtype=torch.int) for el in batch], dim=0)
+    rewards = torch.stack([torch.tensor(el.rewards) for el in batch], dim=0)
+    dones = torch.stack([torch.tensor(el.dones) for el in batch], dim=0)
+    return CodedBatch(torch.from_numpy(np.concatenate(files)), torch.from_numpy(offsets.astype(np.int32)), hw, sources, torch.stack(slots, dim=0), actions, rewards, dones,
+                      batch[0].spec, [el.video for el in batch], [el.initial_frame_index for el in batch])
+
+
 def collate_fn_for(element):
-    """the collate function of a dataset whose items look like `element`: raw elements, BatchElements, or None for anything else"""
+    """the collate function of a dataset whose items look like `element`: coded or raw elements, BatchElements, or None for anything else"""
+    if isinstance(element, CodedBatchElement):
+        return coded_batch_elements_collate_fn
     if isinstance(element, RawBatchElement):
         return raw_batch_elements_collate_fn
     return single_batch_elements_collate_fn if is_batch_element(element) else None

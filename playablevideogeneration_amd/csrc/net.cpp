@@ -10,6 +10,7 @@
 #include "sheets.h"
 #include "video.h"
 #include "png.h"
+#include "png_read.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1686,6 +1687,7 @@ void caddy_ctx_destroy(caddy_ctx* c) {
     sheets_free(c);
     video_free(c);
     png_free(c);
+    png_read_free(c);
     delete c;
 }
 int caddy_set_stream(caddy_ctx* c, void* s) { c->stream = (hipStream_t)s; return 0; }

@@ -72,7 +72,8 @@ enum { CTX_MODEL = 1,       // caddy_ctx_create
        CTX_FRAMES = 64,     // caddy_frames_ctx_create (frames.hip: uint8 frames -> observations; no model, no weights)
        CTX_SHEETS = 128,    // caddy_sheets_ctx_create (sheets.hip: evaluation example sheets; no model, no weights)
        CTX_VIDEO = 256,     // caddy_video_ctx_create (video.hip: baseline JPEG encoder of the MJPEG video writer; no model, no weights)
-       CTX_PNG = 512 };     // caddy_png_ctx_create (png.hip: PNG filter + deflate of the PNG writer; no model, no weights)
+       CTX_PNG = 512,       // caddy_png_ctx_create (png.hip: PNG filter + deflate of the PNG writer; no model, no weights)
+       CTX_PNG_READ = 1024 };      // caddy_png_read_ctx_create (png_read.hip: PNG parse + inflate + unfilter of the PNG reader; no model, no weights)
 
 struct BNL;
 #define CADDY_N_FLAGS 128
@@ -263,6 +264,7 @@ struct caddy_ctx {
     struct SheetsState* sh = nullptr;       // evaluation example sheets (caddy_sheets_ctx_create; sheets.hip owns it)
     struct VideoState* vid = nullptr;       // MJPEG video writer (caddy_video_ctx_create; video.hip owns it)
     struct PngState* png = nullptr;         // PNG writer (caddy_png_ctx_create; png.hip owns it)
+    struct PngReadState* png_read = nullptr;      // PNG reader (caddy_png_read_ctx_create; png_read.hip owns it)
 
     // ---- optional per-launch timing of the conv kernels (HIP events on the launch stream; bench.py roofline) ----
     struct ProfRec { hipEvent_t a, b; int fam; double flops; int P, K, Cout, KS, kind; double bytes; };   // kind: 0 fwd, 1 dgrad (accumulate), 2 wgrad

@@ -82,7 +82,7 @@ class DatasetEvaluator:
         from torch.utils.data import DataLoader
         from .batching import collate_fn_for, single_batch_elements_collate_fn
 
-        def collate(ds):      # raw elements (evaluation.device_transforms) bring their own collate function
+        def collate(ds):      # raw and coded elements (evaluation.device_transforms / device_decode) bring their own collate function; their batches decode in to_tuple()
             return (collate_fn_for(ds[0]) if len(ds) else None) or single_batch_elements_collate_fn
         self.reference_dataloader = DataLoader(reference_dataset, batch_size=b["batch_size"], shuffle=False, collate_fn=collate(reference_dataset),
                                                num_workers=b.get("num_workers", 0), pin_memory=torch.cuda.is_available())

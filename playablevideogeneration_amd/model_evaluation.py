@@ -21,7 +21,7 @@ import torch
 
 from . import metrics as M
 from .action_samplers import OneHotActionSampler, ZeroActionVariationSampler
-from .batching import raw_batch_elements_collate_fn
+from .batching import coded_batch_elements_collate_fn, raw_batch_elements_collate_fn
 from .drivers import DEFAULT_DATASET_EVALUATOR, _factory
 from .evaluation_dataset_builder import sequence_metadata
 from .frame_pipeline import MAP_IF_NEGATIVE, cached_pipeline, cached_writer
@@ -52,14 +52,15 @@ class DeviceBatch:
 
 class ModelRollouts:
     """Iterable with __len__ over the TEST split: (reference DeviceBatch, generated DeviceBatch) per batch of evaluation.batching.batch_size sequences.  The dataset is read
-    through `raw_frame_spec` whatever `data.device_transforms` says (the workers only decode); the roll-out is the builder's: `ground_truth_observations_init` from
-    `evaluation_dataset`, OneHotActionSampler, ZeroActionVariationSampler, temperature `gumbel_temperature_end`, eval mode."""
+    through `raw_frame_spec` whatever `data.device_transforms` says (the workers only decode, or with `data.device_decode` only read the files); the roll-out is the
+    builder's: `ground_truth_observations_init` from `evaluation_dataset`, OneHotActionSampler, ZeroActionVariationSampler, temperature `gumbel_temperature_end`, eval mode."""
 
     def __init__(self, config, model, dataset, logger):
         self.config, self.model, self.logger = config, model, logger
         size = config["model"]["representation_network"]["target_input_size"]
         self.dataset = copy.copy(dataset)      # the same videos and sample grid, undecorated frames
-        self.dataset.final_transform = raw_frame_spec(config["data"].get("crop"), size, 0)
+        self.device_decode = bool(config["data"].get("device_decode", False))      # opt-in: the workers ship the PNG files, the device decodes them (png_reader.py)
+        self.dataset.final_transform = raw_frame_spec(config["data"].get("crop"), size, 0, "device" if self.device_decode else "host")
         self.ground_truth_observations_init = config["evaluation_dataset"]["ground_truth_observations_init"]
         self.temperature = config["training"]["gumbel_temperature_end"]
         b = config["evaluation"]["batching"]
@@ -75,8 +76,8 @@ class ModelRollouts:
 
     def _loader(self):
         from torch.utils.data import DataLoader
-        return DataLoader(self.dataset, batch_size=self.batch_size, shuffle=False, collate_fn=raw_batch_elements_collate_fn, num_workers=self.num_workers,
-                          pin_memory=self.device.type == "cuda")
+        collate = coded_batch_elements_collate_fn if self.device_decode else raw_batch_elements_collate_fn
+        return DataLoader(self.dataset, batch_size=self.batch_size, shuffle=False, collate_fn=collate, num_workers=self.num_workers, pin_memory=self.device.type == "cuda")
 
     def __iter__(self):
         model = self.model
@@ -90,10 +91,10 @@ class ModelRollouts:
             model.train(was_training)
 
     def pair(self, raw):
-        """one RawBatch -> (reference DeviceBatch, generated DeviceBatch)"""
+        """one RawBatch (or CodedBatch: its files are decoded on the device first) -> (reference DeviceBatch, generated DeviceBatch)"""
         dev = self.device
-        n, h, w = (int(v) for v in raw.frames.shape[:3])
-        frames = raw.frames.to(dev, non_blocking=True)      # staged once, read by both pipelines
+        n, (h, w) = raw.n_frames, raw.frame_hw
+        frames = raw.device_frames(tuple(t.to(dev, non_blocking=True) for t in raw.staged()), self.lib, dev)      # staged (and, as files, decoded) once, read by both pipelines
         bs, T, S = raw.slot_src.shape
         to_model = cached_pipeline(h, w, raw.spec.crop, raw.spec.size, 0, n, self.lib, dev)
         to_metric = cached_pipeline(h, w, raw.spec.crop, raw.spec.size, 1, n, self.lib, dev)

@@ -8,8 +8,8 @@ thread over raw uint8 frames).
     cached_png_encoder  the encoder of a library, device, geometry and filter mode
     save_png            one image to a path
 
-Not built: a general LZ77 match finder (the matches are distance-1 runs, as zlib's Z_RLE strategy finds them), palette / grey / 16-bit / alpha images, interlacing, a
-decoder.  There is no host fallback: the kernels of the library in use (libcaddy_hip.so, or the tests' host simulator) are the only encoder.
+Not built: a general LZ77 match finder (the matches are distance-1 runs, as zlib's Z_RLE strategy finds them), palette / grey / 16-bit / alpha images, interlacing (the
+decoder is png_reader.py).  There is no host fallback: the kernels of the library in use (libcaddy_hip.so, or the tests' host simulator) are the only encoder.
 """
 import ctypes as C
 from typing import List, Sequence

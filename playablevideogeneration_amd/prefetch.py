@@ -7,7 +7,8 @@ the consumer's stream waits on -- the copy of batch i+1 overlaps the training st
         trainer.compute_losses(model, batch_tuple, ...)
 
 A `batching.RawBatch` (device transforms) is staged as what it is -- the distinct uint8 frames and the int32 slot list, a quarter or less of the fp32 bytes -- and the
-frame pipeline's kernel runs on the prefetch stream behind the copies; the consumer sees the same tuple under the same event.
+frame pipeline's kernel runs on the prefetch stream behind the copies; the consumer sees the same tuple under the same event.  A `batching.CodedBatch` (device decode)
+is staged as the bytes of its PNG files and their offsets, and the decoder's kernel runs on the prefetch stream in front of the pipeline's.
 """
 from typing import Iterable, Iterator, Optional, Tuple
 
@@ -38,8 +39,9 @@ class DevicePrefetcher:
         raw = batch if hasattr(batch, "slot_src") and hasattr(batch, "observations") else None
         if raw is not None:      # frames and slots travel as they are; the observations are made on this stream, behind their copies
             from .frame_pipeline import validate_slots
-            validate_slots(raw.slot_src, int(raw.frames.shape[0]))
-            items = (raw.frames, raw.slot_src, raw.actions, raw.rewards, raw.dones)
+            validate_slots(raw.slot_src, raw.n_frames)
+            head = raw.staged()      # the uint8 frames, or the PNG files' bytes and their offsets
+            items = head + (raw.slot_src, raw.actions, raw.rewards, raw.dones)
         else:
             items = _as_tuple(batch)
         out = []
@@ -54,14 +56,17 @@ class DevicePrefetcher:
             if self.pin and not t.is_pinned() and t.device.type == "cpu":
                 key = (slot, i)
                 buf = self._pinned.get(key)
-                if buf is None or buf.shape != t.shape or buf.dtype != t.dtype:
+                grows = t.dim() == 1 and buf is not None and buf.dim() == 1 and buf.numel() >= t.numel()      # a byte blob changes its length from batch to batch
+                if buf is None or buf.dtype != t.dtype or (buf.shape != t.shape and not grows):
                     buf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
                     self._pinned[key] = buf
-                buf.copy_(t)
-                src = buf
+                src = buf if buf.shape == t.shape else buf[:t.numel()]
+                src.copy_(t)
             out.append(src.to(self.device, non_blocking=True))
         if raw is not None:
-            out = [raw.observations(out[0], out[1], device=self.device if self.on_gpu else None)] + out[2:]
+            device = self.device if self.on_gpu else None
+            frames = raw.device_frames(tuple(out[:len(head)]), device=device)
+            out = [raw.observations(frames, out[len(head)], device=device)] + out[len(head) + 1:]
         return tuple(out)
 
     def __iter__(self) -> Iterator[Tuple]:

@@ -9,7 +9,9 @@
 By default frames are decoded and transformed with PIL on the host (DataLoader workers), stacked by the collate function and moved by `Batch.to_tuple()` /
 `DevicePrefetcher`.  With `raw_frame_spec(...)` in place of a transform (`data.device_transforms` / `evaluation.device_transforms`) the workers only decode: the
 dataset yields `RawBatchElement`s of distinct uint8 frames, and crop, resize, normalisation and stacking run on the GPU as one HIP kernel when the batch is turned
-into its tuple (batching.RawBatch, frame_pipeline.py, csrc/frames.hip) -- same bits, a quarter or less of the bytes.  `EvaluationVideo.save`
+into its tuple (batching.RawBatch, frame_pipeline.py, csrc/frames.hip) -- same bits, a quarter or less of the bytes.  With `raw_frame_spec(..., decode="device")`
+(`data.device_decode` / `evaluation.device_decode`) the workers do not decode either: they read each distinct frame's PNG file and ship its bytes
+(batching.CodedBatch), and the device inflates and unfilters them (png_reader.py, csrc/png_read.hip) in front of that kernel.  `EvaluationVideo.save`
 (evaluation_dataset_builder.py) writes the same format this module reads.
 """
 import glob
@@ -21,7 +23,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from .batching import BatchElement, RawBatchElement, accumulated_rewards, available_samples, normalize_frame, observation_indices
+from .batching import BatchElement, CodedBatchElement, RawBatchElement, accumulated_rewards, available_samples, normalize_frame, observation_indices
 
 ANNOTATION_FILES = ("actions", "rewards", "metadata", "dones")
 
@@ -59,6 +61,16 @@ class VideoOnDisk:
 
     def get_frames_count(self) -> int:
         return len(self.actions)
+
+    def frame_path(self, idx: int) -> str:
+        return os.path.join(self.frames_path, f"{idx:05d}.{self.extension}")
+
+    def read_frame_bytes(self, idx: int) -> bytes:
+        """the file of frame idx as it lies on disk"""
+        if idx < 0 or idx >= len(self.actions):
+            raise Exception(f"Index {idx} is out of range")
+        with open(self.frame_path(idx), "rb") as f:
+            return f.read()
 
     def get_frame_at(self, idx: int):
         """PIL image of frame idx; transparent images are flattened onto white like the reference does (dataset/video.py:158-175)"""
@@ -110,18 +122,22 @@ def evaluation_transform(crop, target_input_size) -> Callable:
 
 class RawFrameSpec:
     """Marker a VideoDataset takes in place of a transform: its frames leave the dataset undecorated and `crop` ([left, upper, right, lower] or None), the resize to
-    `size` ((width, height)) and the normalisation of `mode` (0: final_transform's [-1, 1], 1: evaluation_transform's [0, 1]) run on the device."""
+    `size` ((width, height)) and the normalisation of `mode` (0: final_transform's [-1, 1], 1: evaluation_transform's [0, 1]) run on the device.  `decode`: "host"
+    (the workers decode with PIL and ship uint8 frames) or "device" (they ship the PNG files' bytes, png_reader.py decodes them on the device)."""
 
-    def __init__(self, crop, size, mode: int):
+    def __init__(self, crop, size, mode: int, decode: str = "host"):
         if mode not in (0, 1):
             raise ValueError(f"mode must be 0 ([-1, 1]) or 1 ([0, 1]), got {mode}")
+        if decode not in ("host", "device"):
+            raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
+        self.decode = decode
         self.crop = None if crop is None else tuple(int(v) for v in crop)
         self.size = tuple(int(v) for v in size)
         self.mode = int(mode)
 
 
-def raw_frame_spec(crop, size, mode: int) -> RawFrameSpec:
-    return RawFrameSpec(crop, size, mode)
+def raw_frame_spec(crop, size, mode: int, decode: str = "host") -> RawFrameSpec:
+    return RawFrameSpec(crop, size, mode, decode)
 
 
 class VideoDataset(Dataset):
@@ -183,6 +199,8 @@ class VideoDataset(Dataset):
         """the sample's distinct frames, decoded once each and left as they are, plus where each goes"""
         order = sorted({i for st in stacks for i in st})
         where = {i: k for k, i in enumerate(order)}
+        if self.final_transform.decode == "device":
+            return self._coded_element(video, first, obs_idx, stacks, order, where)
         frames = []
         for i in order:
             image = video.get_frame_at(i)
@@ -191,6 +209,29 @@ class VideoDataset(Dataset):
             frames.append(np.asarray(image, dtype=np.uint8).copy())
         return RawBatchElement(frames, [[where[i] for i in st] for st in stacks], [video.actions[i] for i in obs_idx],
                                accumulated_rewards(video.rewards, obs_idx, self.skip_frames), [video.dones[i] for i in obs_idx], self.final_transform, video, first)
+
+
+    def _coded_element(self, video, first, obs_idx, stacks, order, where) -> CodedBatchElement:
+        """the sample's distinct frames as the bytes of their files; only what the device decoder reads is let through: PNG, 8-bit RGB, not interlaced, one size"""
+        from .png_reader import probe
+        if video.extension.lower() != "png":
+            raise Exception(f"{video.frame_path(order[0])}: the device decoder reads PNG files only (such datasets keep the host decoder)")
+        files, hw = [], None
+        for i in order:
+            data = video.read_frame_bytes(i)
+            try:
+                width, height, depth, colour, interlace = probe(data)
+            except ValueError as e:
+                raise Exception(f"{video.frame_path(i)}: {e}")
+            if (depth, colour, interlace) != (8, 2, 0):      # (the datasets the device transforms refuse as well: PIL would not give mode RGB, or flattens them)
+                raise Exception(f"{video.frame_path(i)}: bit depth {depth}, colour type {colour}, interlace {interlace}; the device decoder takes 8-bit RGB (colour type 2) "
+                                f"frames without interlacing only")
+            if hw is not None and (height, width) != hw:
+                raise Exception(f"{video.frame_path(i)}: {width} x {height}, the frames before it {hw[1]} x {hw[0]}: frames of different sizes in one batch")
+            hw = (height, width)
+            files.append(np.frombuffer(data, np.uint8))
+        return CodedBatchElement(files, hw, [(video.frames_path, i) for i in order], [[where[i] for i in st] for st in stacks], [video.actions[i] for i in obs_idx],
+                                 accumulated_rewards(video.rewards, obs_idx, self.skip_frames), [video.dones[i] for i in obs_idx], self.final_transform, video, first)
 
 
 def generate_splits(config) -> Dict[str, Tuple[str, Dict, Optional[List[str]]]]:
@@ -213,8 +254,9 @@ def generate_splits(config) -> Dict[str, Tuple[str, Dict, Optional[List[str]]]]:
 
 def build_datasets(config) -> Dict[str, VideoDataset]:
     """what train.py:42-51 does before it calls the trainer / evaluator factories"""
-    if config["data"].get("device_transforms", False):      # opt-in: the workers decode, the GPU crops, resizes, normalises and stacks
-        tf = raw_frame_spec(config["data"]["crop"], config["model"]["representation_network"]["target_input_size"], 0)
+    decode = "device" if config["data"].get("device_decode", False) else "host"      # opt-in: the workers ship the files, the GPU decodes them (implies device_transforms)
+    if decode == "device" or config["data"].get("device_transforms", False):      # opt-in: the workers decode, the GPU crops, resizes, normalises and stacks
+        tf = raw_frame_spec(config["data"]["crop"], config["model"]["representation_network"]["target_input_size"], 0, decode)
     else:
         tf = final_transform(config)
     return {k: VideoDataset(path, batching, tf, allowed) for k, (path, batching, allowed) in generate_splits(config).items()}
