@@ -661,6 +661,22 @@ int caddy_k_adam(float* p, const float* g, float* m, float* v, long n, float lr,
  *  caddy_k_bn_bwd_reduce, caddy_k_bn_bwd_apply, caddy_k_act_bwd_add, caddy_k_lstm_fwd, caddy_k_lstm_bwd, caddy_k_tanh_bwd,
  *  caddy_k_attn_mul[_bwd], caddy_k_gap[_bwd], caddy_k_colsum, caddy_k_spatial_sum, caddy_k_nchw_to_nhwc, caddy_k_nhwc_to_nchw,
  *  caddy_k_batch_sum -- see csrc/capi_kernels.cpp for the exact signatures) */
+/* action-network tail, sampling, centroid EMA, their backward, and the loss kernels (csrc/head.h declares the argument structs; reference: model/main_model/action_network.py:86-118,
+ * gumbel_softmax.py:25-72, centroid_estimator.py:38-94, training/losses.py, training/trainer.py:447-500).  Every hook and `lv` may be null. */
+struct HeadBufs; struct HeadParams; struct SampleCfg; struct SamplerHooks; struct SmallLossArgs; struct DiagArgs; struct LossWeights; struct VggLevels;
+int caddy_k_struct_size(int which);      /* sizeof of 0 HeadParams, 1 HeadBufs, 2 SampleCfg, 3 SmallLossArgs, 4 DiagArgs, 5 LossWeights, 6 VggLevels, 7 TV (ctypes mirrors check themselves); else -1 */
+int caddy_k_head_forward(const struct HeadBufs* h, const struct HeadParams* p, int B, int T, void* stream);
+int caddy_k_head_sample(const struct HeadBufs* h, const struct HeadParams* p, const struct SampleCfg* c, int NS, float* cen_sums, void (*hook)(float* device_ptr, int count, void* user),
+                        void* user, const struct SamplerHooks* sh, void* stream);      /* -1 for K > 16, Da > 8 or K + Da > 16 */
+int caddy_k_head_backward(const struct HeadBufs* h, const struct HeadParams* p, const struct SampleCfg* c, int B, int T, int first_call, void* stream);
+int caddy_k_head_softmax(const float* logits, float* prob, float* logp /* nullable */, int NS, int K, void* stream);
+int caddy_k_loss_l1(const struct TV* gt, const struct TV* rec, const struct TV* drec, int f, int t_off, int Tobs, int Trec, float gscale, double* acc, float* gt_out /* nullable */, void* stream);
+int caddy_k_loss_mse(const struct TV* a, const struct TV* b, const struct TV* db, float gscale, double* acc, void* stream);
+int caddy_k_loss_small(const struct SmallLossArgs* a, void (*hook)(float* device_ptr, int count, void* user), void* user, void* stream);
+int caddy_k_loss_finalize(double* acc, const struct LossWeights* w, double n0, double n1, double n2, double nstates, double nhidden, const struct VggLevels* lv, void* stream);
+int caddy_k_loss_diagnostics(const struct DiagArgs* d, const struct TV* states, const struct TV* hidden, void* stream);
+int caddy_k_loss_diff_per_frame(const struct TV* a, int Ta, int a_off, const struct TV* b, int Tb, int C, int sq, double* acc, void* stream);
+int caddy_k_loss_report_flag(unsigned* flags /* [live n | sticky n] */, int n, double* slot, double* total, void* stream);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,61 @@ class PackDesc(C.Structure):
                 ("Cout", C.c_int), ("Cout_pad", C.c_int), ("Ktot", C.c_int), ("oscale", C.c_void_p)]
 
 
+# ---- csrc/head.h, csrc/perceptual.h: argument structs of the action head, sampling and loss kernels (caddy_k_head_* / caddy_k_loss_*) ----
+AUX_LD = 16
+LOSS_SLOTS = 56
+LOSS_SLOT = dict(total=0, rec=1, states=2, entropy=3, dir_kl=4, mi=5, state_kl=6, hidden=7, l1_r0=8, l1_r1=9, l1_r2=10, perceptual=11, perceptual_term=12,
+                 f16_saturated=13, perc_r0=16, diag_0=40)
+_FP = C.c_void_p      # device pointers: always c_void_p (a bare int would be truncated to a C int when passed by value)
+
+
+class HeadParams(C.Structure):
+    _fields_ = [("F", C.c_int), ("Da", C.c_int), ("K", C.c_int)] + [(n, _FP) for n in ("Wm", "bm", "Wv", "bv", "Wf", "bf", "dWm", "dbm", "dWv", "dbv", "dWf", "dbf")]
+
+
+class HeadBufs(C.Structure):
+    _fields_ = [(n, _FP) for n in ("feat", "eps_s", "eps_d", "unif", "mu", "raw", "sdist", "ssamp", "ddist", "dirs", "logits", "logp", "prob", "ysoft", "samples", "variations", "aux",
+                                   "cen_used", "selected", "d_feat", "d_logits", "d_ddist", "d_sdist", "d_aux", "g_dmu", "g_dvar", "g_mu", "g_raw")]
+
+
+class SampleCfg(C.Structure):
+    _fields_ = [("mode", C.c_int), ("hard", C.c_int), ("training", C.c_int), ("use_variations", C.c_int), ("tau", C.c_float), ("alpha", C.c_float),
+                ("centroids", _FP), ("samples_in", _FP), ("variations_in", _FP)]
+
+
+class SmallLossArgs(C.Structure):
+    _fields_ = [("K", C.c_int), ("Da", C.c_int), ("NS", C.c_int), ("NT", C.c_int), ("Pbuf", _FP), ("mi_grad_scale", C.c_float),
+                ("p", _FP), ("q", _FP), ("logp", _FP), ("ddist", _FP), ("sdist", _FP), ("sdist_r", _FP),
+                ("d_logits", _FP), ("d_logits_r", _FP), ("d_ddist", _FP), ("d_sdist_r", _FP),
+                ("ema", _FP), ("ema_alpha", C.c_float), ("update_ema", C.c_int),
+                ("mi_lamb", C.c_float), ("w_mi", C.c_float), ("w_entropy", C.c_float), ("w_dirkl", C.c_float), ("w_statekl", C.c_float), ("acc", _FP)]
+
+
+class DiagArgs(C.Structure):
+    _fields_ = [("samples", _FP), ("ddist", _FP), ("rdist", _FP), ("variations", _FP), ("centroids", _FP), ("NS", C.c_int), ("K", C.c_int), ("Da", C.c_int), ("acc", _FP)]
+
+
+class LossWeights(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("rec", "states", "entropy", "dir_kl", "mi", "state_kl", "hidden", "mi_entropy_lambda", "perceptual")]
+
+
+class VggLevels(C.Structure):
+    _fields_ = [("numel", (C.c_double * 5) * 3)]
+
+
+ALLREDUCE_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_void_p)      # allreduce_hook_t(float* device_ptr, int count, void* user)
+HEAD_STRUCTS = (HeadParams, HeadBufs, SampleCfg, SmallLossArgs, DiagArgs, LossWeights, VggLevels, TV)      # index = the argument of caddy_k_struct_size
+
+
+def check_head_structs(lib):
+    """The ctypes mirrors above against the library's own sizeof (caddy_k_struct_size): a mirror that has drifted from csrc/head.h raises here instead of corrupting a launch."""
+    for i, cls in enumerate(HEAD_STRUCTS):
+        n = lib.caddy_k_struct_size(i)
+        if n != C.sizeof(cls):
+            raise RuntimeError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, the library's struct is {n}")
+    assert lib.caddy_k_struct_size(len(HEAD_STRUCTS)) == -1
+
+
 def round_up(a, b):
     return (a + b - 1) // b * b
 

@@ -3,6 +3,8 @@
 #include "common.h"
 #include "pointwise.h"
 #include "pack.h"
+#include "head.h"
+#include "perceptual.h"
 
 #define ST(s) ((hipStream_t)(s))
 extern "C" {
@@ -92,4 +94,35 @@ int caddy_k_nchw_to_nhwc(const float* src, long src_sn, const TV* d, void* s) { 
 int caddy_k_nhwc_to_nchw(const TV* src, float* dst, long dst_sn, int acc, void* s) { return pw_nhwc_to_nchw(*src, dst, dst_sn, acc, ST(s)); }
 int caddy_k_bcast_input_grad(const TV* dz, const PackDesc* d, int seg, float* S, float* g, long g_sn, float* dbias, void* s) { return pw_bcast_input_grad(*dz, *d, seg, S, g, g_sn, dbias, ST(s)); }
 int caddy_k_batch_sum(const float* src, long sn, long n_el, int N, float* dst, void* s) { return pw_batch_sum(src, sn, n_el, N, dst, ST(s)); }
+// action head, sampling and the loss kernels (head.hip)
+int caddy_k_struct_size(int which) {      // sizeof of the argument structs the Python tests mirror (playablevideogeneration_amd/_lib.py: HEAD_STRUCTS, in this order); -1: unknown
+    switch (which) {
+        case 0: return (int)sizeof(HeadParams);
+        case 1: return (int)sizeof(HeadBufs);
+        case 2: return (int)sizeof(SampleCfg);
+        case 3: return (int)sizeof(SmallLossArgs);
+        case 4: return (int)sizeof(DiagArgs);
+        case 5: return (int)sizeof(LossWeights);
+        case 6: return (int)sizeof(VggLevels);
+        case 7: return (int)sizeof(TV);
+        default: return -1;
+    }
+}
+int caddy_k_head_forward(const HeadBufs* h, const HeadParams* p, int B, int T, void* s) { return head_forward(*h, *p, B, T, ST(s)); }
+int caddy_k_head_sample(const HeadBufs* h, const HeadParams* p, const SampleCfg* c, int NS, float* cen_sums, allreduce_hook_t hook, void* user, const SamplerHooks* sh, void* s) {
+    return head_sample(*h, *p, *c, NS, cen_sums, hook, user, sh, ST(s));
+}
+int caddy_k_head_backward(const HeadBufs* h, const HeadParams* p, const SampleCfg* c, int B, int T, int first_call, void* s) { return head_backward(*h, *p, *c, B, T, first_call, ST(s)); }
+int caddy_k_head_softmax(const float* logits, float* prob, float* logp, int NS, int K, void* s) { return head_softmax(logits, prob, logp, NS, K, ST(s)); }
+int caddy_k_loss_l1(const TV* gt, const TV* rec, const TV* drec, int f, int t_off, int Tobs, int Trec, float gscale, double* acc, float* gt_out, void* s) {
+    return loss_l1(*gt, *rec, *drec, f, t_off, Tobs, Trec, gscale, acc, gt_out, ST(s));
+}
+int caddy_k_loss_mse(const TV* a, const TV* b, const TV* db, float gscale, double* acc, void* s) { return loss_mse(*a, *b, *db, gscale, acc, ST(s)); }
+int caddy_k_loss_small(const SmallLossArgs* a, allreduce_hook_t hook, void* user, void* s) { return loss_small(*a, hook, user, ST(s)); }
+int caddy_k_loss_finalize(double* acc, const LossWeights* w, double n0, double n1, double n2, double nstates, double nhidden, const VggLevels* lv, void* s) {
+    return loss_finalize(acc, *w, n0, n1, n2, nstates, nhidden, lv, ST(s));
+}
+int caddy_k_loss_diagnostics(const DiagArgs* d, const TV* states, const TV* hidden, void* s) { return loss_diagnostics(*d, *states, *hidden, ST(s)); }
+int caddy_k_loss_diff_per_frame(const TV* a, int Ta, int a_off, const TV* b, int Tb, int C, int sq, double* acc, void* s) { return loss_diff_per_frame(*a, Ta, a_off, *b, Tb, C, sq, acc, ST(s)); }
+int caddy_k_loss_report_flag(unsigned* flags, int n, double* slot, double* total, void* s) { return loss_report_flag(flags, n, slot, total, ST(s)); }
 }
