@@ -1,5 +1,5 @@
 // Evaluation contexts (eval_ctx.h): the shared scaffold, and the frame-metric, LPIPS and platform-position entry points built on it.  The FID and Inception Score kinds and their entry points live
-// with their graph in fid.hip.  Nothing here allocates device memory: a context lives in the caller's workspace.
+// with their graph in fid.hip, the FVD kind in fvd.hip; what the driving of those trunks shares (TrunkState) is here.  Nothing here allocates device memory: a context lives in the caller's workspace.
 #include "eval_ctx.h"
 #include "frame_metrics.h"
 #include "detection.h"
@@ -63,6 +63,35 @@ bool range_guard_retry(caddy_ctx* c, int flag0, int count) {
     for (int i = 0; i < count; i++) if (v[i] && !c->layer_fallback[flag0 + i]) { c->layer_fallback[flag0 + i] = true; c->n_fallback++; again = true; }
     if (again) hipMemsetAsync(c->sat_flag, 0, FLAG_BYTES, c->stream);
     return again;
+}
+
+TrunkState::TrunkState() {
+    if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) precision = PREC_FP32;
+}
+TrunkState::~TrunkState() {
+    for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+}
+PackedConv TrunkState::alloc_layer(caddy_ctx* c, size_t weight_bytes, int cout) {
+    PackedConv L;
+    L.w32 = c->persist.alloc(weight_bytes); L.w16 = c->persist.alloc(weight_bytes);
+    L.bias = (float*)c->persist.alloc((size_t)cout * 4);
+    return L;
+}
+int trunk_set_precision(TrunkState& S, int forward, const char* who) {
+    if (forward != PREC_FP32 && forward != PREC_F16X3) { set_error(std::string(who) + ": 0 (exact fp32) | 16 (split f16)"); return -2; }
+    S.precision = forward;
+    return 0;
+}
+int trunk_stage_ms(caddy_ctx* c, TrunkState& S, int on, float* ms, int stages, const char* who) {
+    if (ms) {
+        if (!S.timed_ran) { set_error(std::string(who) + ": no timed chunk has run"); return -2; }
+        hipStreamSynchronize(c->stream);
+        for (int k = 0; k < stages; k++) hipEventElapsedTime(ms + k, S.ev[k], S.ev[k + 1]);
+    }
+    if (on && !S.ev[0]) for (int k = 0; k <= stages; k++) hipEventCreate(&S.ev[k]);
+    S.timed = on != 0;
+    if (!on) S.timed_ran = false;
+    return 0;
 }
 
 // The two VGG kinds read the VGG switches of the environment once, when a context is created (c null: creation failed)

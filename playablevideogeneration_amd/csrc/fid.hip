@@ -3,16 +3,12 @@
 // and keeps the 2048 pool_3 values per frame.  This file holds the kernels no other part of the library has (a general implicit-GEMM convolution, the 3x3 poolings, the global
 // average, the 299 x 299 bilinear input stage), the walk over the 94 convolutions, and the C ABI of the FID context.
 //
-// k_conv_igemm.  Workgroup = 256 threads = 2 x 2 waves on a 64 pixel x 64 channel tile, one 32 x 32 accumulator block per wave.  K runs over (tap, 32-channel chunk).  Per K step
-// every thread fetches 8 consecutive channels of one tile pixel (two 16-byte loads; bounds, padding and the channel tail give zeros), one step AHEAD of the matrix instructions
-// (register prefetch), and stores them to LDS in operand form: fp32 for the exact path, an f16 (hi, lo) pair of planes for the split path (hi = f16(x), lo = f16(x - hi), |x|
-// clamped to the f16 range with the sticky flag of ConvArgs.sat_flag).  The weight fragments never pass through LDS: igemm_pack lays them out FRAGMENT-MAJOR (per tap, chunk and
-// 32-channel block the 64 lanes' 16-byte pieces in lane order), so a wave reads each with one fully coalesced 1 KiB load that the other tiles of the launch find in L2.
-// Split f16: acc += hi_a hi_w + hi_a lo_w + lo_a hi_w with the weights pre-scaled by HX_WSCALE (common.h) and the accumulator scaled back in the epilogue.
-// Row padding of the LDS tiles (36 floats / 40 halves per 32 channels) makes the 16-byte fragment reads of 16 consecutive rows hit 16 distinct bank quads.
+// k_conv_igemm is the tile of conv_igemm.h with K running over (tap, 32-channel chunk); a thread finds the tap and chunk of a K step by division.  The Cin = 3 first layer gathers
+// its whole 27-element window from the pitch-4 image into ONE K chunk.
 //
 // Determinism: no atomics except the integer OR of the range flag; every output element has one writer and a fixed summation order, so two runs -- and two chunkings of the same
 // frames -- give identical bits.
+#include "conv_igemm.h"
 #include "eval_ctx.h"
 #include "fid.h"
 #include <cstdio>
@@ -20,120 +16,39 @@
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-#define IG_F16_MAX 65504.f
-constexpr int IG_BM = 64, IG_BN = 64, IG_KC = 32;
-constexpr int IG_LDF = 36;      // floats per LDS row (fp32 operands)
-constexpr int IG_LDH = 40;      // halves per LDS row and plane (split f16 operands)
-
 template <bool F16>
 __global__ __launch_bounds__(256) void k_conv_igemm(IgemmArgs a) {
-    __shared__ __attribute__((aligned(16))) float smem[F16 ? (2 * IG_BM * IG_LDH) / 2 : IG_BM * IG_LDF];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
     const int hw = a.Ho * a.Wo;
     const long M = (long)a.N * hw;
-    const long m0 = (long)blockIdx.x * IG_BM;
-    const int ncb = (int)gridDim.y * 2, cb = (int)blockIdx.y * 2 + wn;      // 32-channel blocks of the packed weights / this wave's block
     // ---- loader role: tile pixel lrow, channels 8 lq .. 8 lq + 7 of the chunk ----
-    const int lrow = tid >> 2, lq = tid & 3;
-    const long lm = m0 + lrow;
+    const int lrow = threadIdx.x >> 2, lq = threadIdx.x & 3;
+    const long lm = (long)blockIdx.x * CG_BM + lrow;
     const bool lvalid = lm < M;
     int ln = 0, loy = 0, lox = 0;
     if (lvalid) { ln = (int)(lm / hw); const int rem = (int)(lm - (long)ln * hw); loy = rem / a.Wo; lox = rem - loy * a.Wo; }
     const float* lbase = a.in + (long)ln * a.in_sn;
     const int iy0 = loy * a.stride - a.ph, ix0 = lox * a.stride - a.pw;
-    const int nsteps = a.gather ? 1 : a.KH * a.KW * a.nchunk;
-    float4 r0, r1;
-#define IG_LOAD(step_)                                                                                                                                  \
-    do {                                                                                                                                                \
-        r0 = make_float4(0.f, 0.f, 0.f, 0.f); r1 = r0;                                                                                                  \
-        if (a.gather) {                                                                                                                                 \
-            float v[8];                                                                                                                                 \
-            for (int e = 0; e < 8; e++) {                                                                                                               \
-                const int k = lq * 8 + e, t = k / a.Cin, cc = k - t * a.Cin, ky = t / a.KW, kx = t - ky * a.KW;                                         \
-                const int iy = iy0 + ky, ix = ix0 + kx;                                                                                                 \
-                v[e] = (lvalid && t < a.KH * a.KW && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi) ? lbase[((long)iy * a.Wi + ix) * a.in_ld + cc] : 0.f; \
-            }                                                                                                                                           \
-            r0 = make_float4(v[0], v[1], v[2], v[3]); r1 = make_float4(v[4], v[5], v[6], v[7]);                                                         \
-        } else {                                                                                                                                        \
-            const int tap = (step_) / a.nchunk, ch = (step_) - tap * a.nchunk, ky = tap / a.KW, kx = tap - ky * a.KW;                                   \
-            const int iy = iy0 + ky, ix = ix0 + kx, c = ch * IG_KC + lq * 8;                                                                            \
-            if (lvalid && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi && c < a.Cin) {                                                                  \
-                const float4* p = reinterpret_cast<const float4*>(lbase + ((long)iy * a.Wi + ix) * a.in_ld + c);                                        \
-                r0 = p[0]; r1 = p[1];                                                                                                                   \
-            }                                                                                                                                           \
-        }                                                                                                                                               \
-    } while (0)
-
-    f32x16 acc;
-    for (int r = 0; r < 16; r++) acc[r] = 0.f;
-    unsigned sat = 0;
-    IG_LOAD(0);
-    for (int step = 0; step < nsteps; step++) {
-        // ---- registers -> LDS in operand form ----
-        if (F16) {
-            _Float16* sh = reinterpret_cast<_Float16*>(smem);
-            const float x[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-            h8 hi, lo;
+    auto load = [&](int step, float4& r0, float4& r1) {
+        r0 = make_float4(0.f, 0.f, 0.f, 0.f); r1 = r0;
+        if (a.gather) {
+            float v[8];
             for (int e = 0; e < 8; e++) {
-                const float t = __builtin_amdgcn_fmed3f(x[e], -IG_F16_MAX, IG_F16_MAX);
-                if (!(t == x[e])) sat |= (x[e] != x[e]) ? 3u : 1u;
-                hi[e] = (_Float16)t;
-                lo[e] = (_Float16)(t - (float)hi[e]);
+                const int k = lq * 8 + e, t = k / a.Cin, cc = k - t * a.Cin, ky = t / a.KW, kx = t - ky * a.KW;
+                const int iy = iy0 + ky, ix = ix0 + kx;
+                v[e] = (lvalid && t < a.KH * a.KW && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi) ? lbase[((long)iy * a.Wi + ix) * a.in_ld + cc] : 0.f;
             }
-            *reinterpret_cast<h8*>(sh + lrow * IG_LDH + lq * 8) = hi;
-            *reinterpret_cast<h8*>(sh + (IG_BM + lrow) * IG_LDH + lq * 8) = lo;
+            r0 = make_float4(v[0], v[1], v[2], v[3]); r1 = make_float4(v[4], v[5], v[6], v[7]);
         } else {
-            float4* d = reinterpret_cast<float4*>(smem + lrow * IG_LDF + lq * 8);
-            d[0] = r0; d[1] = r1;
-        }
-        __syncthreads();
-        if (step + 1 < nsteps) IG_LOAD(step + 1);
-        // ---- matrix instructions: this wave's 32 pixels x 32 channels over the chunk ----
-        const int arow = wm * 32 + (lane & 31), half = lane >> 5;
-        const long wt = ((long)step * ncb + cb);      // (tap, chunk, channel block) tile of the packed weights
-        if (F16) {
-            const _Float16* sh = reinterpret_cast<const _Float16*>(smem);
-            const h8* wq = reinterpret_cast<const h8*>(a.w) + wt * 256 + lane;      // [K half kk][plane][lane]
-#pragma unroll
-            for (int kk = 0; kk < 2; kk++) {
-                const h8 ah = *reinterpret_cast<const h8*>(sh + arow * IG_LDH + kk * 16 + half * 8);
-                const h8 al = *reinterpret_cast<const h8*>(sh + (IG_BM + arow) * IG_LDH + kk * 16 + half * 8);
-                const h8 bh = wq[(kk * 2 + 0) * 64], bl = wq[(kk * 2 + 1) * 64];
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-            }
-        } else {
-            const float4* wp = reinterpret_cast<const float4*>(a.w) + wt * 256 + lane;      // [g][lane]: channels 16 half + 4 g .. + 3
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const float4 av = *reinterpret_cast<const float4*>(smem + arow * IG_LDF + half * 16 + 4 * g);
-                const float4 bv = wp[g * 64];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
+            const int tap = step / a.nchunk, ch = step - tap * a.nchunk, ky = tap / a.KW, kx = tap - ky * a.KW;
+            const int iy = iy0 + ky, ix = ix0 + kx, c = ch * CG_KC + lq * 8;
+            if (lvalid && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi && c < a.Cin) {
+                const float4* p = reinterpret_cast<const float4*>(lbase + ((long)iy * a.Wi + ix) * a.in_ld + c);
+                r0 = p[0]; r1 = p[1];
             }
         }
-        __syncthreads();
-    }
-#undef IG_LOAD
-    if (F16 && sat && a.sat_flag) atomicOr(a.sat_flag, sat);
-    // ---- epilogue: D fragment map col = lane & 31 (output channel), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (pixel of the tile) ----
-    const int o = cb * 32 + (lane & 31);
-    if (o >= a.Cout) return;
-    const float b = a.bias ? a.bias[o] : 0.f;
-    const float sc = F16 ? 1.f / HX_WSCALE : 1.f;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const long m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (m >= M) continue;
-        const long n = m / hw, rem = m - n * hw;
-        float v = acc[r] * sc + b;
-        if (a.relu) v = v > 0.f ? v : 0.f;
-        a.out[n * a.out_sn + rem * a.out_ld + o] = v;
-    }
+    };
+    const ConvTile t{a.w, a.Cout, a.bias, a.relu, a.out, a.out_sn, a.out_ld, a.sat_flag, M, hw, a.gather ? 1 : a.KH * a.KW * a.nchunk};
+    conv_igemm_tile<F16>(t, load);
 }
 
 // one thread per padded (tap, chunk, channel block, channel of the chunk, output channel of the block) element: both packed forms + the folded bias
@@ -145,24 +60,14 @@ __global__ __launch_bounds__(256) void k_igemm_pack(const float* w, const float*
         const int cb = (int)(tile % ncb); const long tc = tile / ncb;
         const int ch = (int)(tc % nchunk), tap = (int)(tc / nchunk);
         const int o = cb * 32 + ol;
-        double s = 1.0;
-        if (gamma && o < Cout) s = (double)gamma[o] / sqrt((double)var[o] + (double)eps);
+        const double s = o < Cout ? conv_fold_scale(gamma, mean, var, eps, o) : 1.0;
         float v = 0.f;
         if (o < Cout) {
             if (gather) { const int t = cl / Cin, cc = cl - t * Cin; if (t < KH * KW) v = (float)((double)w[((long)o * Cin + cc) * KH * KW + t] * s); }
             else { const int c = ch * 32 + cl; if (c < Cin) v = (float)((double)w[((long)o * Cin + c) * KH * KW + tap] * s); }
         }
-        if (w32) {      // [g = (cl & 15) >> 2][lane = 32 (cl >> 4) + ol][e = cl & 3]
-            w32[tile * 1024 + ((((cl & 15) >> 2) * 64 + (cl >> 4) * 32 + ol) * 4 + (cl & 3))] = v;
-        }
-        if (w16) {      // [kk = cl >> 4][plane][lane = 32 ((cl >> 3) & 1) + ol][e = cl & 7], values x HX_WSCALE
-            const float vs = v * HX_WSCALE;
-            const _Float16 hi = (_Float16)vs, lo = (_Float16)(vs - (float)hi);
-            const long base = tile * 2048 + (long)(cl >> 4) * 1024 + (((cl >> 3) & 1) * 32 + ol) * 8 + (cl & 7);
-            w16[base] = hi; w16[base + 512] = lo;
-        }
-        if (bias_out && tc == 0 && cl == 0 && o < Cout)
-            bias_out[o] = gamma ? (float)((double)beta[o] - (double)mean[o] * s) : (bias_in ? bias_in[o] : 0.f);
+        conv_pack_store(w32, w16, tile, cl, ol, v);
+        if (bias_out && tc == 0 && cl == 0 && o < Cout) bias_out[o] = conv_fold_bias(beta, mean, bias_in, s, o);
     }
 }
 
@@ -256,14 +161,11 @@ __global__ __launch_bounds__(256) void k_is_softmax(const float* logits, float* 
     for (int c = lane; c < C; c += 64) p[c] = expf(z[c] - mx) / s;
 }
 
-inline unsigned grid_for(long items) { long b = (items + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
-inline int launch_ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
-
 }  // namespace
 
 size_t igemm_weight_bytes(int Cin, int Cout, int KH, int KW) {
     const long taps = igemm_gather(Cin, KH, KW) ? 1 : KH * KW;
-    return (size_t)taps * igemm_nchunk(Cin, KH, KW) * IG_KC * round_up(Cout, IG_BN) * 4;
+    return (size_t)taps * igemm_nchunk(Cin, KH, KW) * CG_KC * round_up(Cout, CG_BN) * 4;
 }
 
 int igemm_pack(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps, const float* bias_in, int Cin, int Cout, int KH, int KW,
@@ -274,7 +176,7 @@ int igemm_pack(const float* w, const float* gamma, const float* beta, const floa
     if (!gather && (Cin % 8)) return -1;
     const long total = (long)(igemm_weight_bytes(Cin, Cout, KH, KW) / 4);
     hipLaunchKernelGGL(k_igemm_pack, dim3(grid_for(total)), dim3(256), 0, st, w, gamma, beta, mean, var, eps, bias_in, Cin, Cout, KH, KW, gather,
-                       igemm_nchunk(Cin, KH, KW), round_up(Cout, IG_BN) / 32, total, (float*)w32, (_Float16*)w16, bias_out);
+                       igemm_nchunk(Cin, KH, KW), round_up(Cout, CG_BN) / 32, total, (float*)w32, (_Float16*)w16, bias_out);
     return launch_ok();
 }
 
@@ -285,7 +187,7 @@ int igemm_launch(const IgemmArgs& a, hipStream_t st) {
     if (!a.gather && ((a.Cin % 8) || (a.in_ld % 4) || ((uintptr_t)a.in & 15) || (a.in_sn % 4))) return -1;      // 16-byte loads of 8-channel groups
     if (a.precision != PREC_FP32 && a.precision != PREC_F16X3) return -1;
     const long M = (long)a.N * a.Ho * a.Wo;
-    const dim3 g((unsigned)cdiv(M, IG_BM), (unsigned)(round_up(a.Cout, IG_BN) / IG_BN));
+    const dim3 g((unsigned)cdiv(M, CG_BM), (unsigned)(round_up(a.Cout, CG_BN) / CG_BN));
     if (a.precision == PREC_FP32) hipLaunchKernelGGL((k_conv_igemm<false>), g, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_conv_igemm<true>), g, dim3(256), 0, st, a);
     return launch_ok();
@@ -338,19 +240,15 @@ int is_softmax_launch(const float* logits, float* probs, int n, int C, long ld_i
 enum { FLAVOUR_FID = 0,      // pytorch_fid's patched network to pool_3
        FLAVOUR_TV = 1 };     // torchvision's inception_v3(transform_input=False).eval() to the softmax (evaluation/metrics/inception_score.py:20-22,41-43)
 struct FidSpec { char name[96]; int cin, cout, kh, kw, stride, ph, pw; int linear; };      // linear: nn.Linear as a 1 x 1 convolution (weight + bias, no BatchNorm, no ReLU)
-struct FidLayer { FidSpec s; void* w32 = nullptr; void* w16 = nullptr; float* bias = nullptr; long off = 0; };
-struct FidState {
+struct FidLayer : PackedConv { FidSpec s; long off = 0; };
+struct FidState : TrunkState {
     int resize = 1, Hn = 299, Wn = 299;      // size the trunk runs at
     int flavour = FLAVOUR_FID;
     std::vector<FidLayer> L;
-    bool loaded = false;
-    int precision = PREC_F16X3;
     double* feat = nullptr;                  // max_frames x 2048
     float *feat32 = nullptr, *logits = nullptr, *probs = nullptr;      // FLAVOUR_TV: the narrowed features (fc's input), max_frames x 1000 logits and probabilities
     TV taps[3]{};                            // block outputs 0 .. 2 of the last chunk (InceptionV3.BLOCK_INDEX_BY_DIM: 64, 192, 768 channels)
     int last_nf = 0;
-    hipEvent_t ev[7] = {};
-    bool timed = false, timed_ran = false;
 };
 
 namespace {
@@ -575,10 +473,8 @@ EvalKind fid_kind(int max_frames, int H, int W, int resize, int flavour = FLAVOU
                 F->resize = resize ? 1 : 0; F->Hn = resize ? 299 : H; F->Wn = resize ? 299 : W;
                 long off = 0;
                 for (const FidSpec& s : fid_specs(flavour)) {
-                    FidLayer L; L.s = s; L.off = off; off += fid_layer_floats(s);
-                    const size_t wb = igemm_weight_bytes(s.cin, s.cout, s.kh, s.kw);
-                    L.w32 = c->persist.alloc(wb); L.w16 = c->persist.alloc(wb);
-                    L.bias = (float*)c->persist.alloc((size_t)s.cout * 4);
+                    FidLayer L{TrunkState::alloc_layer(c, igemm_weight_bytes(s.cin, s.cout, s.kh, s.kw), s.cout), s, off};
+                    off += fid_layer_floats(s);
                     F->L.push_back(L);
                 }
                 F->feat = (double*)c->persist.alloc(sizeof(double) * FID_DIM * (size_t)max_frames);
@@ -596,10 +492,6 @@ bool fid_ctx_ok(caddy_ctx* c, const char* who, int kind = CTX_FID) {
     c->fail = false;
     return true;
 }
-caddy_ctx* fid_env(caddy_ctx* c) {      // CADDY_PRECISION of the environment, read once when a context is created (c null: creation failed)
-    if (c) if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) c->fid->precision = PREC_FP32;
-    return c;
-}
 int fid_load(caddy_ctx* c, const float* flat, const char* sizer) {
     if (!flat) { set_error("null input"); return -2; }
     for (FidLayer& L : c->fid->L) {
@@ -613,43 +505,15 @@ int fid_load(caddy_ctx* c, const float* flat, const char* sizer) {
     c->fid->loaded = !c->fail;
     return finish(c, sizer);
 }
-int fid_set_precision(caddy_ctx* c, int forward, const char* who) {
-    if (forward != PREC_FP32 && forward != PREC_F16X3) { set_error(std::string(who) + ": 0 (exact fp32) | 16 (split f16)"); return -2; }
-    c->fid->precision = forward;
-    return 0;
-}
-// every chunk of n frames through the walk; a layer of the split-f16 path that left the f16 range moves to exact fp32 and the chunk runs again.  copy(n0, nf) fetches a chunk's result.
+// every chunk of n frames through the walk, range-guarded (trunk_run_chunks).  copy(n0, nf) fetches a chunk's result.
 template <class Copy> void fid_run_chunks(caddy_ctx* c, const float* frames, int n, Copy copy) {
-    FidState* F = c->fid;
     const long fr = 3L * c->cfg.height * c->cfg.width;
-    for_chunks(c, n, [&](long n0, int nf) {      // (the activation arena holds max_frames frames)
-        for (int attempt = 0; attempt < 2; attempt++) {
-            fid_chunk(c, frames + n0 * fr, nf);
-            if (c->fail) return false;
-            if (F->precision == PREC_FP32 || !range_guard_retry(c, 0, (int)F->L.size())) break;
-        }
-        copy(n0, nf);
-        hipStreamSynchronize(c->stream);
-        return true;
-    });
-}
-int fid_stage_ms(caddy_ctx* c, int on, float* ms, int stages, const char* who) {
-    FidState* F = c->fid;
-    if (ms) {
-        if (!F->timed_ran) { set_error(std::string(who) + ": no timed chunk has run"); return -2; }
-        hipStreamSynchronize(c->stream);
-        for (int k = 0; k < stages; k++) hipEventElapsedTime(ms + k, F->ev[k], F->ev[k + 1]);
-    }
-    if (on && !F->ev[0]) for (hipEvent_t& e : F->ev) hipEventCreate(&e);
-    F->timed = on != 0;
-    if (!on) F->timed_ran = false;
-    return 0;
+    trunk_run_chunks(c, *c->fid, n, (int)c->fid->L.size(), [&](long n0, int nf) { fid_chunk(c, frames + n0 * fr, nf); }, copy);
 }
 }  // namespace
 
 void fid_free(caddy_ctx* c) {
-    if (!c || !c->fid) return;
-    for (hipEvent_t e : c->fid->ev) if (e) hipEventDestroy(e);
+    if (!c) return;
     delete c->fid;
     c->fid = nullptr;
 }
@@ -659,7 +523,7 @@ size_t caddy_fid_workspace_bytes(int max_frames, int height, int width, int resi
     return fid_args_ok(max_frames, height, width, resize) ? eval_workspace_bytes(fid_kind(max_frames, height, width, resize)) : 0;
 }
 caddy_ctx* caddy_fid_ctx_create(int max_frames, int height, int width, int resize, void* workspace, size_t bytes) {
-    return fid_args_ok(max_frames, height, width, resize) ? fid_env(eval_ctx_create(fid_kind(max_frames, height, width, resize), workspace, bytes)) : nullptr;
+    return fid_args_ok(max_frames, height, width, resize) ? eval_ctx_create(fid_kind(max_frames, height, width, resize), workspace, bytes) : nullptr;
 }
 int caddy_fid_param_count(void) { return fid_param_count(FLAVOUR_FID); }
 long caddy_fid_param_floats(void) { return fid_param_floats(FLAVOUR_FID); }
@@ -670,7 +534,7 @@ int caddy_load_fid_inception(caddy_ctx* c, const float* flat) {
 }
 int caddy_set_fid_precision(caddy_ctx* c, int forward) {
     if (!fid_ctx_ok(c, "caddy_set_fid_precision")) return -2;
-    return fid_set_precision(c, forward, "caddy_set_fid_precision");
+    return trunk_set_precision(*c->fid, forward, "caddy_set_fid_precision");
 }
 int caddy_fid_features(caddy_ctx* c, const float* frames, int n, double* out_host) {
     if (!fid_ctx_ok(c, "caddy_fid_features")) return -2;
@@ -694,7 +558,7 @@ int caddy_debug_fid_fallback_layers(caddy_ctx* c) { return (c && c->kind == CTX_
 /* on: the next chunks record events at the stage boundaries; ms5 (nullable) receives resize, stem, 35 x 35, 17 x 17 and 8 x 8 times of the LAST chunk */
 int caddy_debug_fid_stage_ms(caddy_ctx* c, int on, float* ms5) {
     if (!fid_ctx_ok(c, "caddy_debug_fid_stage_ms")) return -2;
-    return fid_stage_ms(c, on, ms5, 5, "caddy_debug_fid_stage_ms");
+    return trunk_stage_ms(c, *c->fid, on, ms5, 5, "caddy_debug_fid_stage_ms");
 }
 double caddy_fid_macs_per_frame(int height, int width, int resize) {
     std::vector<FidSpec> S; FidWalk w; w.spec = &S;
@@ -716,7 +580,7 @@ size_t caddy_is_workspace_bytes(int max_frames, int height, int width, int resiz
     return fid_args_ok(max_frames, height, width, resize, "caddy_is") ? eval_workspace_bytes(fid_kind(max_frames, height, width, resize, FLAVOUR_TV)) : 0;
 }
 caddy_ctx* caddy_is_ctx_create(int max_frames, int height, int width, int resize, void* workspace, size_t bytes) {
-    return fid_args_ok(max_frames, height, width, resize, "caddy_is") ? fid_env(eval_ctx_create(fid_kind(max_frames, height, width, resize, FLAVOUR_TV), workspace, bytes)) : nullptr;
+    return fid_args_ok(max_frames, height, width, resize, "caddy_is") ? eval_ctx_create(fid_kind(max_frames, height, width, resize, FLAVOUR_TV), workspace, bytes) : nullptr;
 }
 int caddy_is_param_count(void) { return fid_param_count(FLAVOUR_TV); }
 long caddy_is_param_floats(void) { return fid_param_floats(FLAVOUR_TV); }
@@ -727,7 +591,7 @@ int caddy_load_is_inception(caddy_ctx* c, const float* flat) {
 }
 int caddy_set_is_precision(caddy_ctx* c, int forward) {
     if (!fid_ctx_ok(c, "caddy_set_is_precision", CTX_IS)) return -2;
-    return fid_set_precision(c, forward, "caddy_set_is_precision");
+    return trunk_set_precision(*c->fid, forward, "caddy_set_is_precision");
 }
 int caddy_is_probabilities(caddy_ctx* c, const float* frames, int n, float* out_host) {
     if (!fid_ctx_ok(c, "caddy_is_probabilities", CTX_IS)) return -2;
@@ -749,7 +613,7 @@ int caddy_debug_is_logits(caddy_ctx* c, float* dst) {
 int caddy_debug_is_fallback_layers(caddy_ctx* c) { return (c && c->kind == CTX_IS) ? c->n_fallback : -1; }
 int caddy_debug_is_stage_ms(caddy_ctx* c, int on, float* ms6) {
     if (!fid_ctx_ok(c, "caddy_debug_is_stage_ms", CTX_IS)) return -2;
-    return fid_stage_ms(c, on, ms6, 6, "caddy_debug_is_stage_ms");
+    return trunk_stage_ms(c, *c->fid, on, ms6, 6, "caddy_debug_is_stage_ms");
 }
 double caddy_is_macs_per_frame(int height, int width, int resize) {
     std::vector<FidSpec> S; FidWalk w; w.spec = &S; w.flavour = FLAVOUR_TV;

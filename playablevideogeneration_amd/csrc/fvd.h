@@ -14,7 +14,7 @@ struct V5 {
 
 // Implicit-GEMM forward 3-D convolution: any KT, KH, KW <= 7, strides in {1, 2}, independent LEADING zero padding (pt, ph, pw) with explicit output sizes (TensorFlow's SAME
 // padding is asymmetric: taps outside the input read zero on either side), folded-BatchNorm bias + ReLU in the epilogue.  GEMM view: M = N * To * Ho * Wo output positions (videos
-// and frames are batched into M), N = Cout, K = KT * KH * KW * round_up(Cin, 32).  Tile and arithmetic are those of k_conv_igemm (fid.h).  Cin is a multiple of 8 -- or < 8 with
+// and frames are batched into M), N = Cout, K = KT * KH * KW * round_up(Cin, 32).  Tile and arithmetic are those of k_conv_igemm (conv_igemm.h).  Cin is a multiple of 8 -- or < 8 with
 // `gather`: a pitch-4 image, ONE K chunk per (kt, kh) row of the window (its KW taps x 4 channels are contiguous floats, the weights of the pad lane are zero): K = KT * KH * 32.
 struct Conv3dArgs {
     const float* in; long in_sn; int in_ld; int Cin, Ti, Hi, Wi;

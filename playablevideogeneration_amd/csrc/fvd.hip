@@ -3,13 +3,13 @@
 // the frames to 224 x 224 with TF1's resize_bilinear and maps them to [-1, 1].  This file holds what no other part of the library has -- a 3-D implicit-GEMM convolution, 3-D max
 // pools with SAME padding, the legacy bilinear input stage, the averaging head --, the walk over the 57 convolutions + logits, and the C ABI of the FVD context.
 //
-// k_conv3d_igemm is k_conv_igemm (fid.hip) with one more level of tap indexing: the same 256-thread workgroup = 2 x 2 waves on a 64 position x 64 channel tile, the same register
-// prefetch one K step ahead, the same LDS operand forms and row padding, the same fragment-major weights read straight from global memory, the same split-f16 / exact-fp32
-// arithmetic and range flag.  K runs over (kt, kh, kw, 32-channel chunk); the tap counters advance incrementally (no division in the K loop).  The Cin = 3 first layer gathers one
-// (kt, kh) ROW of the window per K chunk from the pitch-4 image: KW taps x 4 channels = 28 contiguous floats (two 16-byte loads per thread), 49 chunks instead of 343.
+// k_conv3d_igemm is the tile of conv_igemm.h with K running over (kt, kh, kw, 32-channel chunk); the tap counters advance incrementally (no division in the K loop).  The Cin = 3
+// first layer gathers one (kt, kh) ROW of the window per K chunk from the pitch-4 image: KW taps x 4 channels = 28 contiguous floats (two 16-byte loads per thread), 49 chunks
+// instead of 343.
 //
 // Determinism: no atomics except the integer OR of the range flag; every output element has one writer and a fixed summation order (the head sums in fp64 in index order), so two
 // runs -- and two chunkings of the same videos -- give identical bits.
+#include "conv_igemm.h"
 #include "eval_ctx.h"
 #include "fvd.h"
 #include <cstdio>
@@ -17,24 +17,14 @@
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-#define C3_F16_MAX 65504.f
-constexpr int C3_BM = 64, C3_BN = 64, C3_KC = 32;
-constexpr int C3_LDF = 36;      // floats per LDS row (fp32 operands)
-constexpr int C3_LDH = 40;      // halves per LDS row and plane (split f16 operands)
-
 template <bool F16>
 __global__ __launch_bounds__(256) void k_conv3d_igemm(Conv3dArgs a) {
-    __shared__ __attribute__((aligned(16))) float smem[F16 ? (2 * C3_BM * C3_LDH) / 2 : C3_BM * C3_LDF];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
     const int hw = a.Ho * a.Wo;
     const long thw = (long)a.To * hw;
     const long M = (long)a.N * thw;
-    const long m0 = (long)blockIdx.x * C3_BM;
-    const int ncb = (int)gridDim.y * 2, cb = (int)blockIdx.y * 2 + wn;      // 32-channel blocks of the packed weights / this wave's block
     // ---- loader role: tile position lrow, channels 8 lq .. 8 lq + 7 of the chunk (gather: taps 2 lq, 2 lq + 1 of the row) ----
-    const int lrow = tid >> 2, lq = tid & 3;
-    const long lm = m0 + lrow;
+    const int lrow = threadIdx.x >> 2, lq = threadIdx.x & 3;
+    const long lm = (long)blockIdx.x * CG_BM + lrow;
     const bool lvalid = lm < M;
     int ln = 0, lot = 0, loy = 0, lox = 0;
     if (lvalid) {
@@ -44,10 +34,8 @@ __global__ __launch_bounds__(256) void k_conv3d_igemm(Conv3dArgs a) {
     }
     const float* lbase = a.in + (long)ln * a.in_sn;
     const int it0 = lot * a.st - a.pt, iy0 = loy * a.sh - a.ph, ix0 = lox * a.sw - a.pw;
-    const int nsteps = a.gather ? a.KT * a.KH : a.KT * a.KH * a.KW * a.nchunk;
     int kt = 0, ky = 0, kx = 0, ch = 0;      // tap and chunk of the NEXT load
-    float4 r0, r1;
-    auto load = [&]() {
+    auto load = [&](int, float4& r0, float4& r1) {
         r0 = make_float4(0.f, 0.f, 0.f, 0.f); r1 = r0;
         const int it = it0 + kt, iy = iy0 + ky;
         const bool row_ok = lvalid && it >= 0 && it < a.Ti && iy >= 0 && iy < a.Hi;
@@ -60,7 +48,7 @@ __global__ __launch_bounds__(256) void k_conv3d_igemm(Conv3dArgs a) {
             }
             if (++ky == a.KH) { ky = 0; kt++; }
         } else {
-            const int ix = ix0 + kx, c = ch * C3_KC + lq * 8;
+            const int ix = ix0 + kx, c = ch * CG_KC + lq * 8;
             if (row_ok && ix >= 0 && ix < a.Wi && c < a.Cin) {
                 const float4* p = reinterpret_cast<const float4*>(lbase + (((long)it * a.Hi + iy) * a.Wi + ix) * a.in_ld + c);
                 r0 = p[0]; r1 = p[1];
@@ -68,78 +56,11 @@ __global__ __launch_bounds__(256) void k_conv3d_igemm(Conv3dArgs a) {
             if (++ch == a.nchunk) { ch = 0; if (++kx == a.KW) { kx = 0; if (++ky == a.KH) { ky = 0; kt++; } } }
         }
     };
-
-    f32x16 acc;
-    for (int r = 0; r < 16; r++) acc[r] = 0.f;
-    unsigned sat = 0;
-    load();
-    for (int step = 0; step < nsteps; step++) {
-        // ---- registers -> LDS in operand form ----
-        if (F16) {
-            _Float16* sh = reinterpret_cast<_Float16*>(smem);
-            const float x[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-            h8 hi, lo;
-            for (int e = 0; e < 8; e++) {
-                const float t = __builtin_amdgcn_fmed3f(x[e], -C3_F16_MAX, C3_F16_MAX);
-                if (!(t == x[e])) sat |= (x[e] != x[e]) ? 3u : 1u;
-                hi[e] = (_Float16)t;
-                lo[e] = (_Float16)(t - (float)hi[e]);
-            }
-            *reinterpret_cast<h8*>(sh + lrow * C3_LDH + lq * 8) = hi;
-            *reinterpret_cast<h8*>(sh + (C3_BM + lrow) * C3_LDH + lq * 8) = lo;
-        } else {
-            float4* d = reinterpret_cast<float4*>(smem + lrow * C3_LDF + lq * 8);
-            d[0] = r0; d[1] = r1;
-        }
-        __syncthreads();
-        if (step + 1 < nsteps) load();
-        // ---- matrix instructions: this wave's 32 positions x 32 channels over the chunk ----
-        const int arow = wm * 32 + (lane & 31), half = lane >> 5;
-        const long wt = ((long)step * ncb + cb);      // (tap, chunk, channel block) tile of the packed weights
-        if (F16) {
-            const _Float16* sh = reinterpret_cast<const _Float16*>(smem);
-            const h8* wq = reinterpret_cast<const h8*>(a.w) + wt * 256 + lane;      // [K half kk][plane][lane]
-#pragma unroll
-            for (int kk = 0; kk < 2; kk++) {
-                const h8 ah = *reinterpret_cast<const h8*>(sh + arow * C3_LDH + kk * 16 + half * 8);
-                const h8 al = *reinterpret_cast<const h8*>(sh + (C3_BM + arow) * C3_LDH + kk * 16 + half * 8);
-                const h8 bh = wq[(kk * 2 + 0) * 64], bl = wq[(kk * 2 + 1) * 64];
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-            }
-        } else {
-            const float4* wp = reinterpret_cast<const float4*>(a.w) + wt * 256 + lane;      // [g][lane]: channels 16 half + 4 g .. + 3
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const float4 av = *reinterpret_cast<const float4*>(smem + arow * C3_LDF + half * 16 + 4 * g);
-                const float4 bv = wp[g * 64];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
-    if (F16 && sat && a.sat_flag) atomicOr(a.sat_flag, sat);
-    // ---- epilogue: D fragment map col = lane & 31 (output channel), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (position of the tile) ----
-    const int o = cb * 32 + (lane & 31);
-    if (o >= a.Cout) return;
-    const float b = a.bias ? a.bias[o] : 0.f;
-    const float sc = F16 ? 1.f / HX_WSCALE : 1.f;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const long m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (m >= M) continue;
-        const long n = m / thw, rem = m - n * thw;
-        float v = acc[r] * sc + b;
-        if (a.relu) v = v > 0.f ? v : 0.f;
-        a.out[n * a.out_sn + rem * a.out_ld + o] = v;
-    }
+    const ConvTile t{a.w, a.Cout, a.bias, a.relu, a.out, a.out_sn, a.out_ld, a.sat_flag, M, thw, a.gather ? a.KT * a.KH : a.KT * a.KH * a.KW * a.nchunk};
+    conv_igemm_tile<F16>(t, load);
 }
 
-// one thread per padded (K chunk, channel block, element of the chunk, output channel of the block) element: both packed forms (the layouts of k_igemm_pack) + the folded bias
+// one thread per padded (K chunk, channel block, element of the chunk, output channel of the block) element: both packed forms + the folded bias
 __global__ __launch_bounds__(256) void k_conv3d_pack(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps, const float* bias_in,
                                                      int Cin, int Cout, int taps, int KW, int gather, int nchunk, int ncb, long total, float* w32, _Float16* w16, float* bias_out) {
     for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -147,22 +68,14 @@ __global__ __launch_bounds__(256) void k_conv3d_pack(const float* w, const float
         const long tile = i >> 10;                       // K chunk * ncb + cb
         const int cb = (int)(tile % ncb); const long kc = tile / ncb;
         const int o = cb * 32 + ol;
-        double s = 1.0;
-        if (mean && o < Cout) s = (gamma ? (double)gamma[o] : 1.0) / sqrt((double)var[o] + (double)eps);
+        const double s = o < Cout ? conv_fold_scale(gamma, mean, var, eps, o) : 1.0;
         long tap = -1; int c = 0;
         if (gather) { const int kx = cl >> 2; c = cl & 3; if (kx < KW && c < Cin) tap = kc * KW + kx; }      // chunk = (kt, kh) row; element = 4 kx + channel, the pad lane is zero
         else { c = (int)(kc % nchunk) * 32 + cl; if (c < Cin) tap = kc / nchunk; }
         float v = 0.f;
         if (o < Cout && tap >= 0 && tap < taps) v = (float)((double)w[(tap * Cin + c) * Cout + o] * s);
-        if (w32) w32[tile * 1024 + ((((cl & 15) >> 2) * 64 + (cl >> 4) * 32 + ol) * 4 + (cl & 3))] = v;
-        if (w16) {
-            const float vs = v * HX_WSCALE;
-            const _Float16 hi = (_Float16)vs, lo = (_Float16)(vs - (float)hi);
-            const long base = tile * 2048 + (long)(cl >> 4) * 1024 + (((cl >> 3) & 1) * 32 + ol) * 8 + (cl & 7);
-            w16[base] = hi; w16[base + 512] = lo;
-        }
-        if (bias_out && kc == 0 && cl == 0 && o < Cout)
-            bias_out[o] = mean ? (float)((double)beta[o] - (double)mean[o] * s) : (bias_in ? bias_in[o] : 0.f);
+        conv_pack_store(w32, w16, tile, cl, ol, v);
+        if (bias_out && kc == 0 && cl == 0 && o < Cout) bias_out[o] = conv_fold_bias(beta, mean, bias_in, s, o);
     }
 }
 
@@ -249,14 +162,12 @@ __global__ __launch_bounds__(256) void k_fvd_stage(const float* src, float* out,
     }
 }
 
-inline unsigned grid_for(long items) { long b = (items + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
-inline int launch_ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 inline bool v5_ok(const V5& v) { return v.p && v.N >= 1 && v.T >= 1 && v.H >= 1 && v.W >= 1 && v.C >= 4 && !(v.C % 4) && !(v.ld % 4) && v.ld >= v.C && !(v.sn % 4) && !((uintptr_t)v.p & 15); }
 
 }  // namespace
 
 size_t conv3d_weight_bytes(int Cin, int Cout, int KT, int KH, int KW) {
-    return (size_t)conv3d_ksteps(Cin, KT, KH, KW) * C3_KC * round_up(Cout, C3_BN) * 4;
+    return (size_t)conv3d_ksteps(Cin, KT, KH, KW) * CG_KC * round_up(Cout, CG_BN) * 4;
 }
 
 int conv3d_pack(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps, const float* bias_in, int Cin, int Cout, int KT, int KH, int KW,
@@ -269,7 +180,7 @@ int conv3d_pack(const float* w, const float* gamma, const float* beta, const flo
     if (gather && Cin > 4) return -1;
     const long total = (long)(conv3d_weight_bytes(Cin, Cout, KT, KH, KW) / 4);
     hipLaunchKernelGGL(k_conv3d_pack, dim3(grid_for(total)), dim3(256), 0, st, w, gamma, beta, mean, var, eps, bias_in, Cin, Cout, KT * KH * KW, KW, gather,
-                       conv3d_nchunk(Cin, KW), round_up(Cout, C3_BN) / 32, total, (float*)w32, (_Float16*)w16, bias_out);
+                       conv3d_nchunk(Cin, KW), round_up(Cout, CG_BN) / 32, total, (float*)w32, (_Float16*)w16, bias_out);
     return launch_ok();
 }
 
@@ -284,8 +195,8 @@ int conv3d_launch(const Conv3dArgs& a, hipStream_t st) {
     if (a.gather ? (a.in_ld != 4 || a.Cin > 4) : (a.Cin % 8) != 0) return -1;
     if (a.precision != PREC_FP32 && a.precision != PREC_F16X3) return -1;
     const long M = (long)a.N * a.To * a.Ho * a.Wo;
-    if (cdiv(M, C3_BM) < 1 || M > (long)C3_BM * 0x7fffffffL) return -1;
-    const dim3 g((unsigned)cdiv(M, C3_BM), (unsigned)(round_up(a.Cout, C3_BN) / C3_BN));
+    if (cdiv(M, CG_BM) < 1 || M > (long)CG_BM * 0x7fffffffL) return -1;
+    const dim3 g((unsigned)cdiv(M, CG_BM), (unsigned)(round_up(a.Cout, CG_BN) / CG_BN));
     if (a.precision == PREC_FP32) hipLaunchKernelGGL((k_conv3d_igemm<false>), g, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_conv3d_igemm<true>), g, dim3(256), 0, st, a);
     return launch_ok();
@@ -315,17 +226,13 @@ int fvd_stage_launch(const float* src, long frames, int Hs, int Ws, float* out, 
 #define FVD_DIM 400
 #define FVD_SIZE 224
 struct FvdSpec { char name[96]; int cin, cout, kt, kh, kw, stride, bn; };      // bn 0: the logits layer (bias, no batch norm, no activation)
-struct FvdLayer { FvdSpec s; void* w32 = nullptr; void* w16 = nullptr; float* bias = nullptr; long off = 0, gamma_off = 0; };
-struct FvdState {
+struct FvdLayer : PackedConv { FvdSpec s; long off = 0, gamma_off = 0; };
+struct FvdState : TrunkState {
     int T = 0, resize = 1, Hn = FVD_SIZE, Wn = FVD_SIZE;      // frames per video; size the trunk runs at
     std::vector<FvdLayer> L;
-    bool loaded = false;
-    int precision = PREC_F16X3;
     double* emb = nullptr;                   // max_videos x 400
     V5 taps[4]{};                            // outputs of Conv3d_2c, Mixed_3c, Mixed_4f, Mixed_5c of the last chunk
     int last_n = 0;
-    hipEvent_t ev[6] = {};
-    bool timed = false, timed_ran = false;
 };
 
 namespace {
@@ -471,11 +378,9 @@ EvalKind fvd_kind(int max_videos, int T, int H, int W, int resize) {
                 F->T = T; F->resize = resize ? 1 : 0; F->Hn = resize ? FVD_SIZE : H; F->Wn = resize ? FVD_SIZE : W;
                 long off = 0, goff = fvd_required_floats();
                 for (const FvdSpec& s : fvd_specs()) {
-                    FvdLayer L; L.s = s; L.off = off; off += fvd_layer_floats(s);
+                    FvdLayer L{TrunkState::alloc_layer(c, conv3d_weight_bytes(s.cin, s.cout, s.kt, s.kh, s.kw), s.cout), s, off};
+                    off += fvd_layer_floats(s);
                     if (s.bn) { L.gamma_off = goff; goff += s.cout; }
-                    const size_t wb = conv3d_weight_bytes(s.cin, s.cout, s.kt, s.kh, s.kw);
-                    L.w32 = c->persist.alloc(wb); L.w16 = c->persist.alloc(wb);
-                    L.bias = (float*)c->persist.alloc((size_t)s.cout * 4);
                     F->L.push_back(L);
                 }
                 F->emb = (double*)c->persist.alloc(sizeof(double) * FVD_DIM * (size_t)max_videos);
@@ -491,8 +396,7 @@ bool fvd_ctx_ok(caddy_ctx* c, const char* who) {
 }  // namespace
 
 void fvd_free(caddy_ctx* c) {
-    if (!c || !c->fvd) return;
-    for (hipEvent_t e : c->fvd->ev) if (e) hipEventDestroy(e);
+    if (!c) return;
     delete c->fvd;
     c->fvd = nullptr;
 }
@@ -502,9 +406,7 @@ size_t caddy_fvd_workspace_bytes(int max_videos, int frames, int height, int wid
     return fvd_args_ok(max_videos, frames, height, width) ? eval_workspace_bytes(fvd_kind(max_videos, frames, height, width, resize)) : 0;
 }
 caddy_ctx* caddy_fvd_ctx_create(int max_videos, int frames, int height, int width, int resize, void* workspace, size_t bytes) {
-    caddy_ctx* c = fvd_args_ok(max_videos, frames, height, width) ? eval_ctx_create(fvd_kind(max_videos, frames, height, width, resize), workspace, bytes) : nullptr;
-    if (c) if (const char* e = getenv("CADDY_PRECISION")) if (!strcmp(e, "exact") || !strcmp(e, "0")) c->fvd->precision = PREC_FP32;
-    return c;
+    return fvd_args_ok(max_videos, frames, height, width) ? eval_ctx_create(fvd_kind(max_videos, frames, height, width, resize), workspace, bytes) : nullptr;
 }
 int caddy_fvd_param_count(void) { int bn = 0; for (const FvdSpec& s : fvd_specs()) bn += s.bn; return fvd_required_params() + bn; }
 long caddy_fvd_param_floats(void) { long n = fvd_required_floats(); for (const FvdSpec& s : fvd_specs()) if (s.bn) n += s.cout; return n; }
@@ -559,9 +461,7 @@ int caddy_load_fvd_i3d(caddy_ctx* c, const float* flat) {
 }
 int caddy_set_fvd_precision(caddy_ctx* c, int forward) {
     if (!fvd_ctx_ok(c, "caddy_set_fvd_precision")) return -2;
-    if (forward != PREC_FP32 && forward != PREC_F16X3) { set_error("caddy_set_fvd_precision: 0 (exact fp32) | 16 (split f16)"); return -2; }
-    c->fvd->precision = forward;
-    return 0;
+    return trunk_set_precision(*c->fvd, forward, "caddy_set_fvd_precision");
 }
 int caddy_fvd_embeddings(caddy_ctx* c, const float* videos, int n, double* out_host) {
     if (!fvd_ctx_ok(c, "caddy_fvd_embeddings")) return -2;
@@ -570,17 +470,8 @@ int caddy_fvd_embeddings(caddy_ctx* c, const float* videos, int n, double* out_h
     FvdState* F = c->fvd;
     if (!F->loaded) { set_error("caddy_fvd_embeddings: no I3D weights were loaded (caddy_load_fvd_i3d)"); return -2; }
     const long vid = 3L * F->T * c->cfg.height * c->cfg.width;
-    for_chunks(c, n, [&](long n0, int nv) {      // (the activation arena holds max_videos videos)
-        // a layer of the split-f16 path that left the f16 range moves to exact fp32 and the chunk runs again
-        for (int attempt = 0; attempt < 2; attempt++) {
-            fvd_chunk(c, videos + n0 * vid, nv);
-            if (c->fail) return false;
-            if (F->precision == PREC_FP32 || !range_guard_retry(c, 0, (int)F->L.size())) break;
-        }
-        hipMemcpyAsync(out_host + n0 * FVD_DIM, F->emb, sizeof(double) * FVD_DIM * nv, hipMemcpyDeviceToHost, c->stream);
-        hipStreamSynchronize(c->stream);
-        return true;
-    });
+    trunk_run_chunks(c, *F, n, (int)F->L.size(), [&](long n0, int nv) { fvd_chunk(c, videos + n0 * vid, nv); },
+                     [&](long n0, int nv) { hipMemcpyAsync(out_host + n0 * FVD_DIM, F->emb, sizeof(double) * FVD_DIM * nv, hipMemcpyDeviceToHost, c->stream); });
     return finish(c, FVD_SIZER);
 }
 int caddy_debug_fvd_block(caddy_ctx* c, int block, float* dst_ncdhw) {
@@ -597,16 +488,7 @@ int caddy_debug_fvd_fallback_layers(caddy_ctx* c) { return (c && c->kind == CTX_
 /* on: the next chunks record events at the stage boundaries; ms5 (nullable) receives input stage, stem, Mixed_3, Mixed_4 and Mixed_5 + head times of the LAST chunk */
 int caddy_debug_fvd_stage_ms(caddy_ctx* c, int on, float* ms5) {
     if (!fvd_ctx_ok(c, "caddy_debug_fvd_stage_ms")) return -2;
-    FvdState* F = c->fvd;
-    if (ms5) {
-        if (!F->timed_ran) { set_error("caddy_debug_fvd_stage_ms: no timed chunk has run"); return -2; }
-        hipStreamSynchronize(c->stream);
-        for (int k = 0; k < 5; k++) hipEventElapsedTime(ms5 + k, F->ev[k], F->ev[k + 1]);
-    }
-    if (on && !F->ev[0]) for (hipEvent_t& e : F->ev) hipEventCreate(&e);
-    F->timed = on != 0;
-    if (!on) F->timed_ran = false;
-    return 0;
+    return trunk_stage_ms(c, *c->fvd, on, ms5, 5, "caddy_debug_fvd_stage_ms");
 }
 double caddy_fvd_macs_per_video(int frames, int height, int width, int resize) {
     if (frames < 1 || height < 1 || width < 1) return 0.0;

@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 import torch.nn.functional as F
 
-from tests.inception_cases import CONV_TOL, rel_l2
+from tests.inception_cases import CONV_TOL, rel_l2, run_conv
 
 BN_EPS = 0.001
 BLOCK_CHANNELS = (192, 480, 832, 1024)
@@ -216,9 +216,10 @@ def ksteps(Cin, k):
     return KT * KH if Cin < 8 else KT * KH * KW * ((Cin + 31) // 32)
 
 
-def run_conv3d(lib, device, x, w, bias, stride, precision, relu=True, ld_extra=0, c0=0, bn=None, sync=None):
+def run_conv3d(lib, device, x, w, bias, stride, precision, relu=True, ld_extra=0, c0=0, bn=None, sync=None, packed=None):
     """x (N, Cin, T, H, W), w OIDHW on the CPU, SAME padding -> the kernel's (N, Cout, To, Ho, Wo) output (written into channels [c0, c0 + Cout) of a map of pitch Cout + ld_extra),
-    the untouched rest of that map, the range flag and the launch's K steps.  bn: (gamma or None, beta, mean, var) folded by the packer instead of `bias`"""
+    the untouched rest of that map, the range flag and the launch's K steps.  bn: (gamma or None, beta, mean, var) folded by the packer instead of `bias`.  packed: a list that
+    receives the packer's fp32 and split-f16 buffers as int32 words"""
     bind_kernels(lib)
     N, Cin, T, H, W = x.shape
     Cout, _, KT, KH, KW = w.shape
@@ -249,6 +250,8 @@ def run_conv3d(lib, device, x, w, bias, stride, precision, relu=True, ld_extra=0
     if sync is not None:
         sync()
     out = out.cpu()
+    if packed is not None:
+        packed += [w32.cpu().view(torch.int32), w16.cpu().view(torch.int32)]
     rest = torch.cat([out[..., :c0], out[..., c0 + Cout:]], -1)
     return out[..., c0:c0 + Cout].permute(0, 4, 1, 2, 3).contiguous(), rest, int(flag.cpu()[0]), ksteps(Cin, (KT, KH, KW))
 
@@ -282,6 +285,35 @@ def conv3d_case(lib, device, case, precision, seed=0, N=2, sync=None):
     assert flag == 0 and err < CONV_TOL, (case, precision, err)
     if Cin == 3 and k == (7, 7, 7):
         assert 32 * steps <= 1.6 * 1029, steps      # the first layer must not pay a 32-channel chunk per tap (343 x 32 = 10 976)
+
+
+# (Cin, Cout, (KH, KW), stride, (ph, pw), H, W): 2-D convolutions whose symmetric padding is also TensorFlow's SAME, so the 3-D kernel runs the same problem with KT = 1, T = 1.
+# The Cin = 3 gather layers are not here: their K layouts differ by design (27-element window against one window row per chunk).
+CROSS_CASES = [
+    (32, 64, (3, 3), 1, (1, 1), 13, 15),        # one full chunk; M = 390 is not a multiple of 64
+    (48, 64, (5, 5), 1, (2, 2), 7, 9),          # chunk tail: 1.5 chunks
+    (64, 80, (1, 1), 1, (0, 0), 9, 11),         # channel-tile tail: Cout = 80
+    (16, 48, (3, 3), 2, (1, 1), 9, 7),          # stride 2, half a chunk, odd sizes
+    (128, 128, (1, 7), 1, (0, 3), 7, 9),        # asymmetric window, four chunks
+]
+
+
+def cross_case(lib, device, case, precision, seed=0, N=2, sync=None):
+    """k_conv_igemm and k_conv3d_igemm walk K in the same order through the same tile body (csrc/conv_igemm.h) where their problems overlap: outputs and packed weights are
+    identical, not close"""
+    Cin, Cout, (KH, KW), stride, (ph, pw), H, W = case
+    assert same_pads(H, KH, stride)[1:] == (ph, ph) and same_pads(W, KW, stride)[1:] == (pw, pw), "the case's padding is not SAME"
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, KH, KW, generator=g) * (2.0 / (Cin * KH * KW)) ** 0.5
+    b = torch.randn(Cout, generator=g) * 0.1
+    p2, p3 = [], []
+    got2, rest2, flag2 = run_conv(lib, device, x, w, b, stride, (ph, pw), precision, relu=True, ld_extra=16, c0=8, sync=sync, packed=p2)
+    got3, rest3, flag3, _ = run_conv3d(lib, device, x[:, :, None], w[:, :, None], b, (1, stride, stride), precision, relu=True, ld_extra=16, c0=8, sync=sync, packed=p3)
+    assert got3.shape == got2.shape[:2] + (1,) + got2.shape[2:] and torch.equal(got2, got3[:, :, 0]), (case, precision, (got2 - got3[:, :, 0]).abs().max().item())
+    assert flag2 == 0 and flag3 == 0 and (got2 > 0).any(), (case, precision, flag2, flag3)
+    assert (rest2 == -7.0).all() and (rest3 == -7.0).all(), "a launch wrote outside its channel slice"
+    assert torch.equal(p2[0], p3[0]) and torch.equal(p2[1], p3[1]), "the two packers lay the same weights out differently"
 
 
 POOL_FORMS = [((1, 3, 3), (1, 2, 2)), ((3, 3, 3), (2, 2, 2)), ((2, 2, 2), (2, 2, 2)), ((3, 3, 3), (1, 1, 1))]

@@ -181,9 +181,9 @@ def bind_kernels(lib):
     return lib
 
 
-def run_conv(lib, device, x, w, bias, stride, pad, precision, relu=True, ld_extra=0, c0=0, sync=None):
+def run_conv(lib, device, x, w, bias, stride, pad, precision, relu=True, ld_extra=0, c0=0, sync=None, packed=None):
     """x (N, Cin, H, W), w OIHW on the CPU -> the kernel's (N, Cout, Ho, Wo) output (written into channels [c0, c0 + Cout) of a map of pitch Cout + ld_extra) and the
-    untouched rest of that map"""
+    untouched rest of that map.  packed: a list that receives the packer's fp32 and split-f16 buffers as int32 words"""
     bind_kernels(lib)
     N, Cin, H, W = x.shape
     Cout, _, KH, KW = w.shape
@@ -207,6 +207,8 @@ def run_conv(lib, device, x, w, bias, stride, pad, precision, relu=True, ld_extr
     if sync is not None:
         sync()
     out = out.cpu()
+    if packed is not None:
+        packed += [w32.cpu().view(torch.int32), w16.cpu().view(torch.int32)]
     rest = torch.cat([out[..., :c0], out[..., c0 + Cout:]], -1)
     return out[..., c0:c0 + Cout].permute(0, 3, 1, 2).contiguous(), rest, int(flag.cpu()[0])
 

@@ -39,6 +39,12 @@ def test_conv3d_igemm_matches_conv3d(emu, case, precision):
     I3.conv3d_case(emu, torch.device("cpu"), case, precision, N=2)
 
 
+@pytest.mark.parametrize("case", I3.CROSS_CASES, ids=lambda c: f"{c[0]}to{c[1]}_k{c[2][0]}x{c[2][1]}_s{c[3]}")
+@pytest.mark.parametrize("precision", [0, 16])
+def test_conv3d_igemm_is_conv_igemm_bit_for_bit(emu, case, precision):
+    I3.cross_case(emu, torch.device("cpu"), case, precision, N=2)
+
+
 def test_pools_match_max_pool3d(emu):
     I3.pool_cases(emu, torch.device("cpu"))
 

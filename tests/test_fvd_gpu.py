@@ -53,6 +53,12 @@ def test_conv3d_igemm_matches_conv3d(lib, dev, precision):
         I3.conv3d_case(lib, dev, case, precision, N=2, sync=sync)
 
 
+@pytest.mark.parametrize("precision", [0, 16])
+def test_conv3d_igemm_is_conv_igemm_bit_for_bit(lib, dev, precision):
+    for case in I3.CROSS_CASES:
+        I3.cross_case(lib, dev, case, precision, N=2, sync=sync)
+
+
 def test_pools_and_stage(lib, dev):
     I3.pool_cases(lib, dev, sync=sync)
     I3.stage_cases(lib, dev, [(64, 64), (208, 160), (224, 224)], sync=sync)
