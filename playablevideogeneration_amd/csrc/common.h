@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -28,6 +29,24 @@ struct TV {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+
+// Host-side state override for one scope: remembers `ref` (and optionally sets it), puts the remembered value back on EVERY exit.  Several guards of a scope restore in reverse
+// order of declaration.
+template <class T> struct Scoped {
+    T& ref; const T old;
+    explicit Scoped(T& r) : ref(r), old(r) {}
+    Scoped(T& r, T v) : ref(r), old(r) { r = v; }
+    ~Scoped() { ref = old; }
+    Scoped(const Scoped&) = delete;
+    Scoped& operator=(const Scoped&) = delete;
+};
+// Runtime bools -> template arguments: with_bools(f, b0, b1, ...) calls the generic lambda f(std::integral_constant<bool, b0>{}, ...), so `decltype(B0)::value` names the
+// kernel instance inside it (one instance per combination; no table to keep in step with the kernel's parameter list)
+template <class F> inline void with_bools(F&& f) { f(); }
+template <class F, class... Bs> inline void with_bools(F&& f, bool b0, Bs... rest) {
+    if (b0) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
 
 // One input segment of a convolution.  A conv reads the channel-concatenation of up to CONV_MAX_SRC segments
 // (reference: ConvLSTMCell.channelwise_concat, convolutional_lstm_cell.py:47-86).  bcast=1: the segment is a

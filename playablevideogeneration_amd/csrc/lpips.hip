@@ -92,11 +92,7 @@ __global__ __launch_bounds__(256) void k_lpips_stage(const float* src, float* ou
 
 template <int NK>
 void head_launch_nk(hipStream_t st, dim3 g, const float* f0, bool s0, const float* f1, bool s1, const float* w, int npix, double* part) {
-    const dim3 b(256);
-    if (s0 && s1) hipLaunchKernelGGL((k_lpips_head<NK, true, true>), g, b, 0, st, f0, f1, w, npix, part);
-    else if (s0) hipLaunchKernelGGL((k_lpips_head<NK, true, false>), g, b, 0, st, f0, f1, w, npix, part);
-    else if (s1) hipLaunchKernelGGL((k_lpips_head<NK, false, true>), g, b, 0, st, f0, f1, w, npix, part);
-    else hipLaunchKernelGGL((k_lpips_head<NK, false, false>), g, b, 0, st, f0, f1, w, npix, part);
+    with_bools([&](auto S0, auto S1) { hipLaunchKernelGGL((k_lpips_head<NK, decltype(S0)::value, decltype(S1)::value>), g, dim3(256), 0, st, f0, f1, w, npix, part); }, s0, s1);
 }
 
 }  // namespace

@@ -683,9 +683,7 @@ T4 caddy_ctx::conv(ConvL& L, const Seg* segs, int nseg, int actf, const T4* into
                 if (Lp->wqd[s] && prec_bwd != PREC_FP32) { d.wq = Lp->wqd[s]; d.precision = PREC_BF16X3; }
                 else if (Lp->pd.Cout <= 3 && Lp->pd.KS == 7 && prec_bwd != PREC_FP32) d.precision = PREC_BF16X3;      // 7x7 FinalBlock head: split bf16 on conv_head.hip (weights split in the kernel)
                 const double dfl = px_taps * sg[s].t.C * Lp->pd.Cout;
-                const int kind_save = prof_kind_override;
-                if (prof_kind_override < 0) prof_kind_override = 1;      // profiling: a dgrad launch, whether it assigns or accumulates
-                struct KindRestore { int& k; int v; ~KindRestore() { k = v; } } kind_restore{prof_kind_override, kind_save};
+                Scoped<int> kind_guard(prof_kind_override, prof_kind_override < 0 ? 1 : prof_kind_override);      // profiling: a dgrad launch, whether it assigns or accumulates
                 if (!sg[s].bcast) {
                     // first-touch inputs (this conv is their only consumer): dgrad assigns -- plain stores, or the deterministic slab split-K when under-filled
                     const bool assign = sg[s].t.nz && !sg[s].t.nz2;      // nz2: a point-wise writer (residual add / up-sampling backward) assigned before this dgrad runs
@@ -698,9 +696,7 @@ T4 caddy_ctx::conv(ConvL& L, const Seg* segs, int nseg, int actf, const T4* into
                         defer_aux([=]() mutable {      // (runs with stream / scratch of the auxiliary stream)
                             d.aux = conv_aux;
                             if (deterministic) { d.split_scratch = conv_split; d.split_cap = conv_split_cap; }
-                            const int keepk = prof_kind_override; prof_kind_override = pk;
-                            RUN(timed_conv_fwd(d, dfl));
-                            prof_kind_override = keepk;
+                            { Scoped<int> kind(prof_kind_override, pk); RUN(timed_conv_fwd(d, dfl)); }
                             if (!Lp->off_ev) hipEventCreateWithFlags(&Lp->off_ev, hipEventDisableTiming);
                             hipEventRecord(Lp->off_ev, stream);
                         });

@@ -61,6 +61,7 @@ struct Arena {
     void reset() { off = 0; top = cap & ~(size_t)255; }
     bool overflow() const { return off > top; }
 };
+struct ArenaMark : Scoped<size_t> { explicit ArenaMark(Arena& a) : Scoped<size_t>(a.off) {} };      // everything bump-allocated in this scope is released on every exit (`old`: the mark)
 
 // Kind of a context, one bit each: an entry point names the kinds it serves (ctx_needs)
 enum { CTX_MODEL = 1,       // caddy_ctx_create
@@ -229,6 +230,9 @@ struct caddy_ctx {
         if (k == 0) { *t0 = perc_t0[kb]; *len = perc_trec - perc_t0[kb]; return true; }
         if (k == kb) { *t0 = 0; *len = perc_t0[kb]; return true; }
         return false;
+    }
+    template <class F> void perc_for_each(F&& f) const {      // f(k, r, t0, len) for every (chunk, level) that has work: chunks in order, levels 0, 1, 2 inside a chunk
+        for (int k = 0; k < perc_nch; k++) for (int r = 0; r < 3; r++) { int t0, len; if (perc_range(r, k, &t0, &len)) f(k, r, t0, len); }
     }
     void perc_plan(int Trec, bool chunked);
     void perc_wait(int t);

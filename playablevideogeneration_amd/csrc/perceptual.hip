@@ -32,7 +32,10 @@ const VggSpec VGG19_SPEC[VGG_NCONV] = {
 const VggSpec LPIPS_SPEC[VGG_NCONV] = {
     {0, 3, 64, 0, -1}, {2, 64, 64, 0, 0}, {5, 64, 128, 1, -1}, {7, 128, 128, 0, 1}, {10, 128, 256, 1, -1}, {12, 256, 256, 0, -1}, {14, 256, 256, 0, 2},
     {17, 256, 512, 1, -1}, {19, 512, 512, 0, -1}, {21, 512, 512, 0, 3}, {24, 512, 512, 1, -1}, {26, 512, 512, 0, -1}, {28, 512, 512, 0, 4}};
-const int LPIPS_C[5] = {64, 128, 256, 512, 512};
+int tap_channels(const VggSpec* VS, int l) {      // channels of feature level l: the width of the conv whose ReLU is tapped
+    for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap == l) return VS[i].cout;
+    return 0;
+}
 
 // MaxPool2d(2, 2) on dense NHWC maps; odd sizes floor like torch (the last row / column is not covered by any window)
 __global__ __launch_bounds__(256) void k_maxpool2(const float* in, float* out, long n_out4, int Hi, int Wi, int C4) {
@@ -224,50 +227,32 @@ T4 valloc(caddy_ctx* c, int N, int H, int W, int C) {      // bottom-up allocati
     float* d = (float*)c->act.alloc((size_t)N * H * W * ld * 4);
     return T4{d, (float*)((char*)d + c->grad_delta), N, H, W, C, (long)H * W * ld, ld, true};
 }
-// format dispatch of the point-wise kernels (S16 flags -> template instances)
+// format dispatch of the point-wise kernels (S16 flags -> template instances: with_bools, common.h)
 void launch_feat_l1(hipStream_t st, const T4& rec, const T4& gt, float seed_w, float* gz, bool gz_s16, double* acc) {
     const long n4 = (long)rec.N * rec.H * rec.W * (rec.C / 4);
-    const dim3 g(grid_for(n4)), b(256);
-    const int k = (rec.fmt ? 4 : 0) | (gt.fmt ? 2 : 0) | ((gz && gz_s16) ? 1 : 0);
-    const float* r = rec.d; const float* t = gt.d;
-    switch (k) {
-        case 0: hipLaunchKernelGGL((k_feat_l1<false, false, false>), g, b, 0, st, r, t, n4, seed_w, gz, acc); break;
-        case 1: hipLaunchKernelGGL((k_feat_l1<false, false, true>), g, b, 0, st, r, t, n4, seed_w, gz, acc); break;
-        case 2: hipLaunchKernelGGL((k_feat_l1<false, true, false>), g, b, 0, st, r, t, n4, seed_w, gz, acc); break;
-        case 3: hipLaunchKernelGGL((k_feat_l1<false, true, true>), g, b, 0, st, r, t, n4, seed_w, gz, acc); break;
-        case 4: hipLaunchKernelGGL((k_feat_l1<true, false, false>), g, b, 0, st, r, t, n4, seed_w, gz, acc); break;
-        case 5: hipLaunchKernelGGL((k_feat_l1<true, false, true>), g, b, 0, st, r, t, n4, seed_w, gz, acc); break;
-        case 6: hipLaunchKernelGGL((k_feat_l1<true, true, false>), g, b, 0, st, r, t, n4, seed_w, gz, acc); break;
-        default: hipLaunchKernelGGL((k_feat_l1<true, true, true>), g, b, 0, st, r, t, n4, seed_w, gz, acc); break;
-    }
+    // (dispatched on the NEGATED flags -- "is plain fp32" -- so that the eight instances are emitted all-fp32 first, the order the code object has always had them in)
+    with_bools([&](auto RF, auto GF, auto ZF) {
+        hipLaunchKernelGGL((k_feat_l1<!decltype(RF)::value, !decltype(GF)::value, !decltype(ZF)::value>), dim3(grid_for(n4)), dim3(256), 0, st, (const float*)rec.d, (const float*)gt.d, n4, seed_w, gz, acc);
+    }, !rec.fmt, !gt.fmt, !(gz && gz_s16));
 }
+int cos_blocks(const T4& f) { const long n4 = (long)f.H * f.W * (f.C / 4); return (int)(n4 / 1024 < 1 ? 1 : (n4 / 1024 > 64 ? 64 : n4 / 1024)); }      // workgroups per image of the per-image kernels
 void launch_feat_l1_img(hipStream_t st, const T4& rec, const T4& gt, double* acc) {
     const long n4 = (long)rec.H * rec.W * (rec.C / 4);
-    const unsigned bx = (unsigned)(n4 / 1024 < 1 ? 1 : (n4 / 1024 > 64 ? 64 : n4 / 1024));
-    const dim3 g(bx, rec.N), b(256);
-    const float* r = rec.d; const float* t = gt.d;
-    if (rec.fmt && gt.fmt) hipLaunchKernelGGL((k_feat_l1_img<true, true>), g, b, 0, st, r, t, n4, acc);
-    else if (rec.fmt) hipLaunchKernelGGL((k_feat_l1_img<true, false>), g, b, 0, st, r, t, n4, acc);
-    else if (gt.fmt) hipLaunchKernelGGL((k_feat_l1_img<false, true>), g, b, 0, st, r, t, n4, acc);
-    else hipLaunchKernelGGL((k_feat_l1_img<false, false>), g, b, 0, st, r, t, n4, acc);
+    with_bools([&](auto RS, auto GS) {
+        hipLaunchKernelGGL((k_feat_l1_img<decltype(RS)::value, decltype(GS)::value>), dim3(cos_blocks(rec), rec.N), dim3(256), 0, st, (const float*)rec.d, (const float*)gt.d, n4, acc);
+    }, rec.fmt != 0, gt.fmt != 0);
 }
-int cos_blocks(const T4& f) { const long n4 = (long)f.H * f.W * (f.C / 4); return (int)(n4 / 1024 < 1 ? 1 : (n4 / 1024 > 64 ? 64 : n4 / 1024)); }
 void launch_feat_cos_img(hipStream_t st, const T4& x, const T4& y, double* part) {
     const long n4 = (long)x.H * x.W * (x.C / 4);
-    const dim3 g(cos_blocks(x), x.N), b(256);
-    if (x.fmt && y.fmt) hipLaunchKernelGGL((k_feat_cos_img<true, true>), g, b, 0, st, x.d, y.d, n4, part);
-    else if (x.fmt) hipLaunchKernelGGL((k_feat_cos_img<true, false>), g, b, 0, st, x.d, y.d, n4, part);
-    else if (y.fmt) hipLaunchKernelGGL((k_feat_cos_img<false, true>), g, b, 0, st, x.d, y.d, n4, part);
-    else hipLaunchKernelGGL((k_feat_cos_img<false, false>), g, b, 0, st, x.d, y.d, n4, part);
+    with_bools([&](auto RS, auto GS) {
+        hipLaunchKernelGGL((k_feat_cos_img<decltype(RS)::value, decltype(GS)::value>), dim3(cos_blocks(x), x.N), dim3(256), 0, st, (const float*)x.d, (const float*)y.d, n4, part);
+    }, x.fmt != 0, y.fmt != 0);
 }
 void launch_maxpool_bwd(hipStream_t st, const T4& pre, const float* gp, bool gz_s16) {
     const long n4 = (long)pre.N * ((pre.H + 1) / 2) * ((pre.W + 1) / 2) * (pre.C / 4);
-    const dim3 g(grid_for(n4)), b(256);
-    const float* a = pre.d;
-    if (pre.fmt && gz_s16) hipLaunchKernelGGL((k_maxpool2_bwd_relu<true, true>), g, b, 0, st, a, gp, pre.g, n4, pre.H, pre.W, pre.C / 4);
-    else if (pre.fmt) hipLaunchKernelGGL((k_maxpool2_bwd_relu<true, false>), g, b, 0, st, a, gp, pre.g, n4, pre.H, pre.W, pre.C / 4);
-    else if (gz_s16) hipLaunchKernelGGL((k_maxpool2_bwd_relu<false, true>), g, b, 0, st, a, gp, pre.g, n4, pre.H, pre.W, pre.C / 4);
-    else hipLaunchKernelGGL((k_maxpool2_bwd_relu<false, false>), g, b, 0, st, a, gp, pre.g, n4, pre.H, pre.W, pre.C / 4);
+    with_bools([&](auto AS, auto ZS) {
+        hipLaunchKernelGGL((k_maxpool2_bwd_relu<decltype(AS)::value, decltype(ZS)::value>), dim3(grid_for(n4)), dim3(256), 0, st, (const float*)pre.d, gp, pre.g, n4, pre.H, pre.W, pre.C / 4);
+    }, pre.fmt != 0, gz_s16);
 }
 }  // namespace
 
@@ -300,16 +285,16 @@ long vgg_param_floats() { return spec_param_floats(VGG19_SPEC); }
 int vgg_param_info(int index, caddy_param_info* out) { return spec_param_info(VGG19_SPEC, index, out); }
 // the LPIPS network (evaluation/metrics/lpips.py:14): the 13 convolutions of its VGG16 trunk under torchvision's names, then the five 1x1 "lin" layers (1, C_l, 1, 1)
 int lpips_param_count() { return 2 * VGG_NCONV + 5; }
-long lpips_param_floats() { long n = spec_param_floats(LPIPS_SPEC); for (int l = 0; l < 5; l++) n += LPIPS_C[l]; return n; }
+long lpips_param_floats() { long n = spec_param_floats(LPIPS_SPEC); for (int l = 0; l < 5; l++) n += tap_channels(LPIPS_SPEC, l); return n; }
 int lpips_param_info(int index, caddy_param_info* out) {
     if (index < 2 * VGG_NCONV) return spec_param_info(LPIPS_SPEC, index, out);
     const int l = index - 2 * VGG_NCONV;
     if (l >= 5) return -1;
     long off = spec_param_floats(LPIPS_SPEC);
-    for (int k = 0; k < l; k++) off += LPIPS_C[k];
+    for (int k = 0; k < l; k++) off += tap_channels(LPIPS_SPEC, k);
     memset(out, 0, sizeof(*out));
     snprintf(out->name, sizeof(out->name), "lin%d.model.1.weight", l);
-    out->offset = off; out->kind = 3; out->ndim = 4; out->shape[0] = 1; out->shape[1] = LPIPS_C[l]; out->shape[2] = out->shape[3] = 1;
+    out->offset = off; out->kind = 3; out->ndim = 4; out->shape[0] = 1; out->shape[1] = tap_channels(LPIPS_SPEC, l); out->shape[2] = out->shape[3] = 1;
     return 0;
 }
 
@@ -337,7 +322,7 @@ void vgg_build(caddy_ctx* c, int kind) {
         }
         L.wq[2] = c->persist.alloc(hx_weight_bytes(d, -1, round_up(d.Cout, hx_pick_bn(d.Cout)), 2));
     }
-    if (kind == VGG_KIND_LPIPS) for (int l = 0; l < 5; l++) V.lin[l] = (float*)c->persist.alloc((size_t)LPIPS_C[l] * 4);
+    if (kind == VGG_KIND_LPIPS) for (int l = 0; l < 5; l++) V.lin[l] = (float*)c->persist.alloc((size_t)tap_channels(VS, l) * 4);
 }
 
 // caddy_load_vgg: `flat` = device buffer laid out per vgg_param_info (torchvision names features.{idx}.weight / .bias, OIHW fp32)
@@ -363,22 +348,27 @@ int vgg_load(caddy_ctx* c, const float* flat) {
         off += nw + round_up(VS[i].cout, 4);
     }
     if (V.kind == VGG_KIND_LPIPS) for (int l = 0; l < 5; l++) {
-        if (!dry) hipLaunchKernelGGL(k_copy_f, dim3(1), dim3(256), 0, c->stream, flat + off, V.lin[l], (long)LPIPS_C[l]);
-        off += LPIPS_C[l];
+        if (!dry) hipLaunchKernelGGL(k_copy_f, dim3(1), dim3(256), 0, c->stream, flat + off, V.lin[l], (long)tap_channels(VS, l));
+        off += tap_channels(VS, l);
     }
     V.loaded = true;
     return c->fail ? -1 : 0;
 }
 
 namespace {
-struct Branch { T4 a[VGG_NCONV]; T4 p[VGG_NCONV]; };      // a[i]: ReLU output of conv i; p[i]: pooled input of conv i (pool_before)
+struct Branch { T4 a[VGG_NCONV]; T4 p[VGG_NCONV]; };      // a walk that is back-propagated: a[i] ReLU output of conv i; p[i] pooled input of conv i (pool_before)
 
 int conv_call(caddy_ctx* c, const ConvArgs& a, double flops, int kind) {
-    int save = c->prof_kind_override;
-    c->prof_kind_override = kind;
-    int rc = c->timed_conv_fwd(a, flops);
-    c->prof_kind_override = save;
-    return rc;
+    Scoped<int> prof_kind(c->prof_kind_override, kind);
+    return c->timed_conv_fwd(a, flops);
+}
+// the five tapped maps of an N x H x W batch (MaxPool2d floors odd sizes); with `b` a second pyramid, allocated level by level behind the first (a[l], b[l], a[l + 1], ...)
+void tap_alloc(caddy_ctx* c, int N, int H, int W, T4* a, T4* b = nullptr) {
+    for (int l = 0; l < 5; l++, H /= 2, W /= 2) {
+        const int C = tap_channels(c->vgg.spec, l);
+        a[l] = valloc(c, N, H, W, C);
+        if (b) b[l] = valloc(c, N, H, W, C);
+    }
 }
 // does the context keep VGG19 feature maps / feature gradients of well-filled layers as S16 tensors?  (both passes on the split-operand kernels: an exact-fp32 pass would have to
 // read them)
@@ -389,11 +379,12 @@ bool vgg_io_ok(const caddy_ctx* c, int i, int N, int H, int W) {
     return vgg_use_s16(c) && VS[i].cin >= 32 && !c->layer_fallback[CADDY_VGG_FLAG0 + i] && conv_hx_s16_ok(N, H, W, VS[i].cout);      // (a layer on the split-bf16 fallback exchanges fp32 tensors)
 }
 
-// 13 x (conv3x3 + bias + ReLU) with the 2x2 max-pools; taps[] (if given) receive the five tapped feature maps in place.
+// 13 x (conv3x3 + bias + ReLU) with the 2x2 max-pools; taps[] (if given) receive the five tapped feature maps in place, and the format each was written in (T4::fmt).
+// keep (the branch that is back-propagated): every full-resolution map is stored, and every map and pooled input is recorded in *keep.
 // Formats (round 5): a feature map is written PRE-SPLIT (S16-f16, T4::fmt) by the epilogue of its producer when that launch and the launch of the convolution that consumes it
 // are both on the S16-capable tile variants (conv_hx_s16_ok: the well-filled ones) -- the consumer then copies operand rows instead of converting every halo element in every
 // one of its output-channel blocks; the point-wise consumers (feature L1, max-pool backward, ReLU masks) read either format.
-void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool keep_all) {
+void vgg_forward(caddy_ctx* c, const T4& img, T4* taps, Branch* keep = nullptr) {
     bool dry = c->dry;
     VggState& V = c->vgg;
     const VggSpec* VS = V.spec;
@@ -403,14 +394,15 @@ void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool ke
     for (int i = 0; i < VGG_NCONV; i++) {
         VggLayer& L = V.conv[i];
         if (VS[i].pool_before) {
-            if (have_pooled) { B.p[i] = pooled; x = pooled; have_pooled = false; }
+            if (have_pooled) { x = pooled; have_pooled = false; }
             else {
                 T4 p = valloc(c, x.N, x.H / 2, x.W / 2, x.C);
                 const long n4 = (long)p.N * p.H * p.W * (p.C / 4);
                 if (x.fmt) { c->fail = true; set_error("internal: S16 feature map handed to the stand-alone max-pool"); }
                 if (!dry) hipLaunchKernelGGL(k_maxpool2, dim3(grid_for(n4)), dim3(256), 0, c->stream, (const float*)x.d, p.d, n4, x.H, x.W, p.C / 4);
-                B.p[i] = p; x = p;
+                x = p;
             }
+            if (keep) keep->p[i] = x;
         }
         T4 out = (taps && VS[i].tap >= 0) ? taps[VS[i].tap] : valloc(c, x.N, x.H, x.W, VS[i].cout);
         out.fmt = 0;
@@ -430,12 +422,12 @@ void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool ke
         a.in_s16 = x.fmt;
         if (x.fmt && !io_here) { c->fail = true; set_error("internal: S16 input for a VGG19 launch that cannot read it"); }
         // MaxPool2d(2, 2) in front of the next conv: written by THIS conv's epilogue on the split-operand kernel (the window's four pixels sit in
-        // one lane) -- no separate pass over the full-resolution map; a branch that is never back-propagated (keep_all = false: the ground truth)
+        // one lane) -- no separate pass over the full-resolution map; a branch that is never back-propagated (no `keep`: the ground truth)
         // does not even store the full-resolution map of such a layer unless it is a tap (VGG19: never, its taps are the first convs AFTER a pool; the VGG16 trunk of LPIPS: always)
         if (pool_next && a.wq && a.precision == PREC_F16X3 && VS[i].cin >= 32 && conv_hx_pool_ok(x.N, x.H, x.W, VS[i].cout)) {
             pooled = valloc(c, x.N, x.H / 2, x.W / 2, VS[i].cout);
             a.pool_out = pooled.d; a.pool_sn = pooled.sn; a.pool_ld = pooled.ld;
-            a.skip_out = (!keep_all && VS[i].tap < 0) ? 1 : 0;
+            a.skip_out = (!keep && VS[i].tap < 0) ? 1 : 0;
             have_pooled = true;
             // the pooled map as S16 when its consumer (conv i + 1 on the pooled geometry) reads S16; the full-resolution map (read by the max-pool backward only) in the same format
             if (io_here && vgg_io_ok(c, i + 1, x.N, x.H / 2, x.W / 2)) { a.pool_s16 = 1; pooled.fmt = 1; if (!a.skip_out) { a.out_s16 = 1; out.fmt = 1; } }
@@ -445,7 +437,9 @@ void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool ke
         }
         a.sat_out_next = ((a.out_s16 || a.pool_s16) && i + 1 < VGG_NCONV) ? 1 : 0;      // a clamped OUTPUT value is the next layer's range problem (flag words are consecutive per layer)
         if (!dry) c->ck(conv_call(c, a, 2.0 * x.N * x.H * x.W * 9.0 * VS[i].cin * VS[i].cout, 3), "vgg conv");
-        B.a[i] = out; x = out;
+        if (taps && VS[i].tap >= 0) taps[VS[i].tap].fmt = out.fmt;      // (a tapped map may be an S16 tensor)
+        if (keep) keep->a[i] = out;
+        x = out;
     }
 }
 }  // namespace
@@ -455,95 +449,71 @@ void vgg_forward(caddy_ctx* c, const T4& img, Branch& B, const T4* taps, bool ke
 // (whose recurrent convolutions on 16x16 / 32x32 maps leave most of the chip idle).  The five tapped maps per resolution stay in the
 // activation arena until caddy_loss_backward; the other feature maps go through one scratch region reused by the three resolutions.
 void vgg_gt_prefetch(caddy_ctx* c, int Trec, int t_off) {
-    bool dry = c->dry;
     const caddy_config& g = c->cfg;
-    const VggSpec* VS = c->vgg.spec;
-    const int tc[5] = {64, 128, 256, 512, 512};
     // chunk table of this forward pass (caddy_ctx::perc_plan): the taps are laid out per chunk, whatever the loss call then does with them.  Pretraining (no BPTT chain to run
     // beside) and evaluation passes keep one chunk.
     c->perc_plan(Trec, c->training && !c->pretraining);
     c->gt_lo = (c->act.off + 255) & ~(size_t)255;
     T4 gimg[caddy_ctx::PERC_MAX_CHUNKS][3];
     // (caddy_ctx::perc_range: the full-resolution level follows the chunk table, the half- and quarter-resolution levels are cut once)
-    for (int k = 0; k < c->perc_nch; k++) {
-        for (int r = 0; r < 3; r++) {
-            int t0, len;
-            if (!c->perc_range(r, k, &t0, &len)) continue;
-            const int N = g.batch * len;
-            int h = g.height >> r, w = g.width >> r;
-            gimg[k][r] = valloc(c, N, h, w, 3);                 // (ld 4)
-            for (int l = 0; l < 5; l++) { c->gt_taps_c[k][r][l] = valloc(c, N, h, w, tc[l]); h /= 2; w /= 2; }
-        }
-    }
+    c->perc_for_each([&](int k, int r, int, int len) {
+        gimg[k][r] = valloc(c, g.batch * len, g.height >> r, g.width >> r, 3);                 // (ld 4)
+        tap_alloc(c, g.batch * len, g.height >> r, g.width >> r, c->gt_taps_c[k][r]);
+    });
     for (int r = 0; r < 3; r++) c->gt_img[r] = gimg[0][r];
     {   // scratch for the non-tapped maps: the largest walk of vgg_forward over EVERY (chunk, level) the side stream will run -- with many short chunks the half of a smaller
         // level that goes with chunk nch / 2 can need more than the longest full-resolution chunk and than the half that goes with chunk 0
         const size_t m0 = c->act.off;
-        const bool was_dry = c->dry; c->dry = true;
         size_t end = m0;
-        for (int k = 0; k < c->perc_nch; k++) for (int r = 0; r < 3; r++) {
-            int t0, len;
-            if (!c->perc_range(r, k, &t0, &len)) continue;
-            Branch G{};
+        Scoped<bool> sizing(c->dry, true);
+        c->perc_for_each([&](int k, int r, int, int) {
             c->act.off = m0;
-            vgg_forward(c, gimg[k][r], G, c->gt_taps_c[k][r], false);
+            vgg_forward(c, gimg[k][r], c->gt_taps_c[k][r]);
             if (c->act.off > end) end = c->act.off;
-        }
+        });
+        // keep the region allocated (the main stream goes on allocating past it: act.off is NOT put back); the side stream re-walks it for every chunk and resolution
         c->act.off = end;
-        c->dry = was_dry;
-        // keep the region allocated (the main stream goes on allocating past it); the side stream re-walks it for every chunk and resolution
-        c->gt_scratch_off = m0; c->gt_scratch_end = c->act.off;
+        c->gt_scratch_off = m0; c->gt_scratch_end = end;
     }
     c->gt_hi = c->act.off;
     c->gt_prefetched = false;
-    if (dry || !c->vgg.loaded || !c->perc_prefetch || !c->training) return;
+    if (c->dry || !c->vgg.loaded || !c->perc_prefetch || !c->training) return;
     c->ensure_side();
     if (!c->use_side || !c->side) return;
-    hipStream_t main_st = c->stream, side = c->wgrad_stream();      // ordered after everything enqueued so far (the NHWC observations)
-    c->stream = side;
-    c->vgg_beside = 1;                                       // (the model's forward pass runs on the main stream meanwhile)
-    for (int k = 0; k < c->perc_nch; k++) {                  // (the order the loss call consumes them in: last time steps first)
-        for (int r = 0; r < 3; r++) {
-            int t0, len;
-            if (!c->perc_range(r, k, &t0, &len)) continue;
+    const hipStream_t side = c->wgrad_stream();             // ordered after everything enqueued so far (the NHWC observations)
+    {
+        Scoped<hipStream_t> on_side(c->stream, side);
+        Scoped<int> beside(c->vgg_beside, 1);                // (the model's forward pass runs on the main stream meanwhile)
+        c->perc_for_each([&](int k, int r, int t0, int len) {      // (the order the loss call consumes them in: last time steps first)
             const T4& gi = gimg[k][r];
             const long npix = (long)gi.N * gi.H * gi.W;
             hipLaunchKernelGGL(k_gt_resize, dim3(grid_for(npix)), dim3(256), 0, side, dv(c->obs), gi.d, gi.H, gi.W, npix, 1 << r, t_off + t0, g.seq_len, len);
-            const size_t keep = c->act.off;
+            ArenaMark keep(c->act);
             c->act.off = c->gt_scratch_off;                    // (host-side bump pointer only: the region is private to the side stream)
-            Branch G{};
-            vgg_forward(c, gi, G, c->gt_taps_c[k][r], false);
+            vgg_forward(c, gi, c->gt_taps_c[k][r]);
             if (c->act.off > c->gt_scratch_end) { c->fail = true; set_error("internal: a ground-truth VGG19 walk passes the side stream's scratch region"); }
-            for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) c->gt_taps_c[k][r][VS[i].tap].fmt = G.a[i].fmt;      // (a tapped map may be an S16 tensor)
-            c->act.off = keep;
-        }
+        });
     }
-    c->vgg_beside = 0;
-    c->stream = main_st;
     hipEventRecord(c->gt_done, side);
     c->gt_prefetched = true;
 }
 
 int caddy_debug_gt_scratch_check(caddy_ctx* c, int trec, long* out) {
     if (!c->cfg.perceptual) { set_error("caddy_debug_gt_scratch_check needs a context created with caddy_config.perceptual = 1"); return -2; }
-    const size_t keep = c->act.off, keep_high = c->act.high;
-    const bool was_dry = c->dry, was_training = c->training, was_pre = c->pretraining;
-    c->dry = true; c->training = true; c->pretraining = false;
+    // a sizing pass in training mode; put back at exit in reverse order of declaration: act.off, act.high (a probe must not raise the high-water mark either), dry, training, pretraining
+    Scoped<bool> pre(c->pretraining, false), training(c->training, true), sizing(c->dry, true);
+    Scoped<size_t> high(c->act.high);
+    ArenaMark keep(c->act);
     vgg_gt_prefetch(c, trec, 1);
     size_t need = 0;
-    for (int k = 0; k < c->perc_nch; k++) for (int r = 0; r < 3; r++) {
-        int t0, len;
-        if (!c->perc_range(r, k, &t0, &len)) continue;
+    c->perc_for_each([&](int k, int r, int, int) {
         const T4& t = c->gt_taps_c[k][r][0];
         const T4 gi = valloc(c, t.N, t.H, t.W, 3);
         c->act.off = c->gt_scratch_off;
-        Branch G{};
-        vgg_forward(c, gi, G, c->gt_taps_c[k][r], false);
+        vgg_forward(c, gi, c->gt_taps_c[k][r]);
         if (c->act.off - c->gt_scratch_off > need) need = c->act.off - c->gt_scratch_off;
-    }
+    });
     out[0] = (long)(c->gt_scratch_end - c->gt_scratch_off); out[1] = (long)need; out[2] = c->perc_nch;
-    c->act.off = keep; c->act.high = keep_high;
-    c->dry = was_dry; c->training = was_training; c->pretraining = was_pre;
     return 0;
 }
 
@@ -569,7 +539,11 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
     const bool par = nch == 1 && !no_par && !dry && c->use_side && c->side != nullptr && !c->prof;
     hipStream_t side = (par || pipe) ? c->wgrad_stream() : st;      // (ordered after the L1 kernels that wrote the seeds / resized ground truth)
     if (pre) { hipStreamWaitEvent(st, c->gt_done, 0); if (pipe) hipStreamWaitEvent(side, c->gt_done, 0); }
-    const size_t mark_all = c->act.off;
+    // put back at exit, in this order: vgg_beside (0 between the driver's entry points), the stream, the arena (everything below is released)
+    ArenaMark all(c->act);
+    Scoped<hipStream_t> stream_guard(c->stream);
+    Scoped<int> beside(c->vgg_beside);
+    const size_t mark_all = all.old;
     size_t side_end = mark_all;                             // memory layout is the parallel one whether or not the levels really overlap (dry-run sizing)
     // Pipelined form: nothing runs beside the FIRST chunk (the tape replay waits for it), so that chunk keeps the level parallelism of the one-pass form -- its full-resolution
     // level on the main stream (in front of the replay's launches), its half- and quarter-resolution levels on the side stream; the later chunks run on the side stream alone,
@@ -601,22 +575,20 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
         }
         // ground-truth branch: keeps only the five tapped maps
         T4 taps[5];
-        Branch G{}, R{};
+        Branch R{};
         if (pre) { for (int l = 0; l < 5; l++) taps[l] = c->gt_taps_c[k][r][l]; }
         else {
-            int h = rec.H, w = rec.W; const int tc[5] = {64, 128, 256, 512, 512};
-            for (int l = 0; l < 5; l++) { taps[l] = valloc(c, rec.N, h, w, tc[l]); h /= 2; w /= 2; }      // MaxPool2d floors odd sizes
+            tap_alloc(c, rec.N, rec.H, rec.W, taps);
             T4 gi = gt_img[r];
             if (!whole) {
                 gi = valloc(c, rec.N, rec.H, rec.W, 3);
                 if (!dry) hipLaunchKernelGGL(k_time_chunk, dim3(grid_for((long)rec.N * F4)), dim3(256), 0, st, (float4*)gt_img[r].d, (float4*)gi.d, F4, Trec, t0, len, (long)rec.N * F4, 0);
             }
-            const size_t mark2 = c->act.off;
-            vgg_forward(c, gi, G, taps, false);
-            for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) taps[VS[i].tap].fmt = G.a[i].fmt;
-            c->act.off = mark2;                  // stream order: the temporaries of the ground-truth branch are dead before anything below overwrites them
+            ArenaMark gt_walk(c->act);           // stream order: the temporaries of the ground-truth branch are dead before anything below overwrites them
+            vgg_forward(c, gi, taps);
         }
-        vgg_forward(c, rec, R, nullptr, true);
+        vgg_forward(c, rec, nullptr, &R);
+        auto input_of = [&](int i) -> const T4& { return VS[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec); };      // what conv i read
         // per-level sums and weights.  w_l = lambda * (l == 0 ? 1 : 2) / 3 / numel_l   (aliasing of level 0 with the total, see the header); numel_l counts ALL B x Trec frames
         float wl[5];
         int li[5];
@@ -626,7 +598,7 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
         // such a launch itself
         bool io_d[VGG_NCONV], gzs[VGG_NCONV];
         for (int i = 0; i < VGG_NCONV; i++) {
-            const T4& in = VS[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec);
+            const T4& in = input_of(i);
             io_d[i] = vgg_use_s16(c) && i > 0 && V.conv[i].wqd[0] != nullptr && conv_hx_s16_ok(in.N, in.H, in.W, VS[i].cin);
         }
         for (int i = 0; i < VGG_NCONV; i++) gzs[i] = io_d[i] && (i + 1 == VGG_NCONV || VS[i + 1].pool_before || io_d[i + 1]);
@@ -640,7 +612,7 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
         auto dgrad_args = [&](int i) {
                 VggLayer& L = V.conv[i];
                 const T4& gz = R.a[i];
-                const T4& in = VS[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec);
+                const T4& in = input_of(i);
                 ConvArgs d{};
                 d.src[0] = ConvSrc{gz.g, gz.sn, gz.ld, L.pd.Cout, L.kd, 0};
                 d.nsrc = 1; d.N = in.N; d.H = in.H; d.W = in.W; d.KS = 3; d.wp = L.wpd; d.Ktot = L.kd;
@@ -674,7 +646,7 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
         if (lambda != 0.0) {
             // backward of the reconstruction branch
             for (int i = VGG_NCONV - 1; i >= 0; i--) {
-                const T4& in = VS[i].pool_before ? R.p[i] : (i > 0 ? R.a[i - 1] : rec);
+                const T4& in = input_of(i);
                 ConvArgs d = dgrad_args(i);
                 if (i > 0 && VS[i - 1].tap >= 0 && l1_fused[VS[i - 1].tap]) d.l1_acc = c->loss_acc + LOSS_PERC_R0 + 6 * r + 1 + VS[i - 1].tap;
                 if (!dry) c->ck(conv_call(c, d, 2.0 * in.N * in.H * in.W * 9.0 * VS[i].cin * VS[i].cout, 4), "vgg dgrad");
@@ -691,15 +663,25 @@ void vgg_perceptual(caddy_ctx* c, double lambda, const T4* gt_img, VggLevels* lv
     }
     if (pipe) hipEventRecord(c->perc_ev[k], side);          // the seeds of the time steps [t0, t0 + len) are final (first chunk: its full-resolution level is ordered by the main stream itself)
     }
-    c->vgg_beside = 0;
-    c->stream = st;
     if (par) {                                               // join: the tape replay reads d(rec_1), d(rec_2)
         hipEvent_t e = c->sev();
         hipEventRecord(e, side);
         hipStreamWaitEvent(st, e, 0);
     }
-    c->act.off = mark_all;
 }
+
+namespace {
+// The walk the three evaluation passes share: the tap pyramids of two staged image batches, interleaved level by level with ta[l] in front of tb[l]; what reserve() allocates
+// behind them (the head's partial sums); the trunk on `ia`, then on `ib` through the same temporaries.  The caller holds the ArenaMark that releases all of it.
+template <class Reserve> int paired_walk(caddy_ctx* c, const T4& ia, const T4& ib, T4* ta, T4* tb, const char* overflow_msg, Reserve&& reserve) {
+    tap_alloc(c, ia.N, ia.H, ia.W, ta, tb);
+    reserve();
+    { ArenaMark first(c->act); vgg_forward(c, ia, ta); }
+    vgg_forward(c, ib, tb);
+    if (c->act.overflow()) { set_error(overflow_msg); return -1; }
+    return 0;
+}
+}  // namespace
 
 // Evaluation: the full-resolution perceptual distance PER RECONSTRUCTED FRAME and feature level -- out_host[l * N + n] = mean |f_l(rec_n) - f_l(gt_n)|, n = b * Trec + t --
 // after a forward pass (any mode).  The reference evaluator applies ParallelPerceptualLoss to one sequence position at a time (evaluation/evaluator.py:55,62,193-197,
@@ -711,42 +693,33 @@ int vgg_eval_per_frame(caddy_ctx* c, double* out_host) {
     const int Trec = c->pretraining ? g.seq_len : g.seq_len - 1, t_off = c->pretraining ? 0 : 1;
     const T4& rec = c->frames[0];
     const int N = rec.N;
-    const VggSpec* VS = c->vgg.spec;
     hipStream_t st = c->stream;
     if (c->gt_prefetched) hipStreamWaitEvent(st, c->gt_done, 0);      // (a training-mode forward started the ground-truth branch on the side stream: its scratch lies below fwd_off, untouched here)
     c->act.off = c->fwd_off;
-    const size_t mark = c->act.off;
-    const int tc[5] = {64, 128, 256, 512, 512};
+    ArenaMark mark(c->act);                                           // (leaves the arena at fwd_off, wherever it stood at entry)
     T4 gi = valloc(c, N, g.height, g.width, 3);
     const long npix = (long)N * g.height * g.width;
     hipLaunchKernelGGL(k_gt_resize, dim3(grid_for(npix)), dim3(256), 0, st, dv(c->obs), gi.d, g.height, g.width, npix, 1, t_off, g.seq_len, Trec);
     T4 tg[5], tr[5];
-    { int h = g.height, w = g.width; for (int l = 0; l < 5; l++) { tg[l] = valloc(c, N, h, w, tc[l]); tr[l] = valloc(c, N, h, w, tc[l]); h /= 2; w /= 2; } }
-    double* acc = c->dalloc(5 * (size_t)N);
-    hipMemsetAsync(acc, 0, sizeof(double) * 5 * (size_t)N, st);
-    const size_t mark2 = c->act.off;
-    { Branch G{}; vgg_forward(c, gi, G, tg, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tg[VS[i].tap].fmt = G.a[i].fmt; }
-    c->act.off = mark2;
-    { Branch R{}; vgg_forward(c, rec, R, tr, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tr[VS[i].tap].fmt = R.a[i].fmt; }
-    if (c->act.overflow()) { c->act.off = mark; set_error("caddy_perceptual_per_frame: workspace too small"); return -1; }
+    double* acc = nullptr;
+    if (paired_walk(c, gi, rec, tg, tr, "caddy_perceptual_per_frame: workspace too small", [&] {
+            acc = c->dalloc(5 * (size_t)N);
+            hipMemsetAsync(acc, 0, sizeof(double) * 5 * (size_t)N, st);
+        })) return -1;
     for (int l = 0; l < 5; l++) launch_feat_l1_img(st, tr[l], tg[l], acc + (size_t)l * N);
     hipMemcpyAsync(out_host, acc, sizeof(double) * 5 * (size_t)N, hipMemcpyDeviceToHost, st);
     hipStreamSynchronize(st);
     for (int l = 0; l < 5; l++) { const double numel = (double)tr[l].H * tr[l].W * tr[l].C; for (int n = 0; n < N; n++) out_host[(size_t)l * N + n] /= numel; }
-    c->act.off = mark;
     return c->fail ? -1 : 0;
 }
 
 // Dataset evaluation (evaluation/metrics/vgg_cosine_similarity.py:22-57, on a metrics context: caddy_metrics_ctx_create): the VGG19 cosine similarity of frames [0, nf) of
-// `ref` / `gen` ((nf, 3, H, W) fp32), out[n] = mean over relu1_1 .. relu5_1 of cos(f_l(ref_n), f_l(gen_n)).  Same walk of the activation arena as vgg_eval_per_frame; with c->dry
-// nothing is launched (workspace sizing).
+// `ref` / `gen` ((nf, 3, H, W) fp32), out[n] = mean over relu1_1 .. relu5_1 of cos(f_l(ref_n), f_l(gen_n)).  With c->dry nothing is launched (workspace sizing).
 int vgg_metric_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, float range, double* out) {
     const bool dry = c->dry;
     const int H = c->cfg.height, W = c->cfg.width;
-    const VggSpec* VS = c->vgg.spec;
     hipStream_t st = c->stream;
-    const size_t mark = c->act.off;
-    const int tc[5] = {64, 128, 256, 512, 512};
+    ArenaMark mark(c->act);
     T4 gr = valloc(c, nf, H, W, 3), gg = valloc(c, nf, H, W, 3);
     const long npix = (long)nf * H * W;
     if (!dry) {
@@ -754,21 +727,17 @@ int vgg_metric_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, f
         hipLaunchKernelGGL(k_metric_stage, dim3(grid_for(npix)), dim3(256), 0, st, gen, gg.d, npix, (long)H * W, range);
     }
     T4 tr[5], tg[5];
-    { int h = H, w = W; for (int l = 0; l < 5; l++) { tr[l] = valloc(c, nf, h, w, tc[l]); tg[l] = valloc(c, nf, h, w, tc[l]); h /= 2; w /= 2; } }
     CosLevels lv{};
-    long total = 0;
-    for (int l = 0; l < 5; l++) { lv.off[l] = total; lv.blocks[l] = cos_blocks(tr[l]); total += (long)nf * lv.blocks[l] * 3; }
-    double* part = c->dalloc((size_t)total);
-    const size_t mark2 = c->act.off;
-    { Branch Rb{}; vgg_forward(c, gr, Rb, tr, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tr[VS[i].tap].fmt = Rb.a[i].fmt; }
-    c->act.off = mark2;
-    { Branch Gb{}; vgg_forward(c, gg, Gb, tg, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tg[VS[i].tap].fmt = Gb.a[i].fmt; }
-    if (c->act.overflow()) { c->act.off = mark; set_error("caddy_frame_metrics: workspace too small"); return -1; }
+    double* part = nullptr;
+    if (paired_walk(c, gr, gg, tr, tg, "caddy_frame_metrics: workspace too small", [&] {
+            long total = 0;
+            for (int l = 0; l < 5; l++) { lv.off[l] = total; lv.blocks[l] = cos_blocks(tr[l]); total += (long)nf * lv.blocks[l] * 3; }
+            part = c->dalloc((size_t)total);
+        })) return -1;
     if (!dry) {
         for (int l = 0; l < 5; l++) launch_feat_cos_img(st, tr[l], tg[l], part + lv.off[l]);
         hipLaunchKernelGGL(k_feat_cos_finalize, dim3((nf + 63) / 64), dim3(64), 0, st, (const double*)part, lv, nf, out);
     }
-    c->act.off = mark;
     return c->fail ? -1 : 0;
 }
 
@@ -778,9 +747,8 @@ int vgg_metric_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, f
 int vgg_lpips_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, float range, double* out, int ldo) {
     const bool dry = c->dry;
     const int H = c->cfg.height, W = c->cfg.width;
-    const VggSpec* VS = c->vgg.spec;
     hipStream_t st = c->stream;
-    const size_t mark = c->act.off;
+    ArenaMark mark(c->act);
     T4 gr = valloc(c, nf, H, W, 3), gg = valloc(c, nf, H, W, 3);
     const long npix = (long)nf * H * W;
     if (!dry) {
@@ -788,16 +756,13 @@ int vgg_lpips_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, fl
         lpips_stage_launch(st, gen, gg.d, npix, (long)H * W, range);
     }
     T4 tr[5], tg[5];
-    { int h = H, w = W; for (int l = 0; l < 5; l++) { tr[l] = valloc(c, nf, h, w, LPIPS_C[l]); tg[l] = valloc(c, nf, h, w, LPIPS_C[l]); h /= 2; w /= 2; } }
     LpipsLevels lv{};
-    long total = 0;
-    for (int l = 0; l < 5; l++) { lv.off[l] = total; lv.blocks[l] = lpips_blocks(tr[l].H * tr[l].W); lv.inv_px[l] = 1.0 / ((double)tr[l].H * tr[l].W); total += (long)nf * lv.blocks[l]; }
-    double* part = c->dalloc((size_t)total);
-    const size_t mark2 = c->act.off;
-    { Branch Rb{}; vgg_forward(c, gr, Rb, tr, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tr[VS[i].tap].fmt = Rb.a[i].fmt; }
-    c->act.off = mark2;
-    { Branch Gb{}; vgg_forward(c, gg, Gb, tg, false); for (int i = 0; i < VGG_NCONV; i++) if (VS[i].tap >= 0) tg[VS[i].tap].fmt = Gb.a[i].fmt; }
-    if (c->act.overflow()) { c->act.off = mark; set_error("caddy_frame_lpips: workspace too small"); return -1; }
+    double* part = nullptr;
+    if (paired_walk(c, gr, gg, tr, tg, "caddy_frame_lpips: workspace too small", [&] {
+            long total = 0;
+            for (int l = 0; l < 5; l++) { lv.off[l] = total; lv.blocks[l] = lpips_blocks(tr[l].H * tr[l].W); lv.inv_px[l] = 1.0 / ((double)tr[l].H * tr[l].W); total += (long)nf * lv.blocks[l]; }
+            part = c->dalloc((size_t)total);
+        })) return -1;
     if (!dry) {
         for (int l = 0; l < 5; l++) {
             if (tr[l].fmt && tg[l].fmt) c->vgg.tap_s16 |= 1u << l;
@@ -805,6 +770,5 @@ int vgg_lpips_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, fl
         }
         lpips_finalize_launch(st, part, lv, nf, out, ldo);
     }
-    c->act.off = mark;
     return c->fail ? -1 : 0;
 }
