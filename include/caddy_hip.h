@@ -664,7 +664,7 @@ int caddy_k_adam(float* p, const float* g, float* m, float* v, long n, float lr,
 /* action-network tail, sampling, centroid EMA, their backward, and the loss kernels (csrc/head.h declares the argument structs; reference: model/main_model/action_network.py:86-118,
  * gumbel_softmax.py:25-72, centroid_estimator.py:38-94, training/losses.py, training/trainer.py:447-500).  Every hook and `lv` may be null. */
 struct HeadBufs; struct HeadParams; struct SampleCfg; struct SamplerHooks; struct SmallLossArgs; struct DiagArgs; struct LossWeights; struct VggLevels;
-int caddy_k_struct_size(int which);      /* sizeof of 0 HeadParams, 1 HeadBufs, 2 SampleCfg, 3 SmallLossArgs, 4 DiagArgs, 5 LossWeights, 6 VggLevels, 7 TV (ctypes mirrors check themselves); else -1 */
+int caddy_k_struct_size(int which);      /* sizeof of 0 HeadParams, 1 HeadBufs, 2 SampleCfg, 3 SmallLossArgs, 4 DiagArgs, 5 LossWeights, 6 VggLevels, 7 TV, 8 LpipsLevels, 9 VggCosArgs (ctypes mirrors check themselves); else -1 */
 int caddy_k_head_forward(const struct HeadBufs* h, const struct HeadParams* p, int B, int T, void* stream);
 int caddy_k_head_sample(const struct HeadBufs* h, const struct HeadParams* p, const struct SampleCfg* c, int NS, float* cen_sums, void (*hook)(float* device_ptr, int count, void* user),
                         void* user, const struct SamplerHooks* sh, void* stream);      /* -1 for K > 16, Da > 8 or K + Da > 16 */
@@ -677,6 +677,26 @@ int caddy_k_loss_finalize(double* acc, const struct LossWeights* w, double n0, d
 int caddy_k_loss_diagnostics(const struct DiagArgs* d, const struct TV* states, const struct TV* hidden, void* stream);
 int caddy_k_loss_diff_per_frame(const struct TV* a, int Ta, int a_off, const struct TV* b, int Tb, int C, int sq, double* acc, void* stream);
 int caddy_k_loss_report_flag(unsigned* flags /* [live n | sticky n] */, int n, double* slot, double* total, void* stream);
+/* point-wise and reduction kernels around the VGG trunks (csrc/perceptual.hip, csrc/lpips.hip; csrc/perceptual.h and lpips.h declare the argument structs), launched through the
+ * drivers' own format dispatch.  Maps are dense NHWC (pitch == C); *_s16 != 0: that operand is an S16 tensor (csrc/common.h: f16 halves for feature maps, bf16 for gradients).
+ * Every entry point validates its arguments first and returns -1 WITHOUT launching for a null pointer, a non-positive size, C % 4 != 0, an S16 operand with C % 32 != 0, a head
+ * width outside {64, 128, 256, 512}, f outside {1, 2, 4} or an observation that is not f times the output, a time window that leaves the sequence, a partial slab too small. */
+struct VggCosArgs; struct LpipsLevels;
+int caddy_k_vgg_maxpool2(const float* in, float* out, int N, int H, int W, int C, void* stream);      /* MaxPool2d(2, 2), fp32; out (N, H / 2, W / 2, C) */
+int caddy_k_vgg_maxpool2_bwd_relu(const float* a, int a_s16, const float* gp, float* gz, int gz_s16, int N, int H, int W, int C, void* stream);      /* gz (N, H, W, C) assigned: gradient of max_pool2d(relu(a), 2) */
+int caddy_k_vgg_feat_l1(const float* rec, int rec_s16, const float* gt, int gt_s16, int N, int H, int W, int C, float seed_w, float* gz /* nullable */, int gz_s16, double* acc,
+                        void* stream);      /* acc[0] += sum |rec - gt|; gz = seed_w sign(rec - gt) where rec > 0, else 0 */
+int caddy_k_vgg_feat_l1_img(const float* rec, int rec_s16, const float* gt, int gt_s16, int N, int H, int W, int C, double* acc, void* stream);      /* acc[n] += image n's sum */
+int caddy_k_vgg_cos_blocks(int H, int W, int C);      /* partial triples per image and level that caddy_k_vgg_feat_cos writes */
+int caddy_k_vgg_feat_cos(const struct VggCosArgs* a, int nf, double* part, long part_doubles, double* out, void* stream);      /* out[n] = mean over the five levels of the cosine similarity */
+int caddy_k_vgg_metric_stage(const float* src, float* out, int N, int H, int W, float range, void* stream);      /* (N, 3, H, W) in [0, range] -> (N, H, W, 4) */
+int caddy_k_vgg_gt_resize(const struct TV* obs, float* out, int Ho, int Wo, int B, int Tobs, int Trec, int t_off, int f, void* stream);      /* out (B * Trec, Ho, Wo, 4) */
+int caddy_k_vgg_time_chunk(float* full, float* chunk, int B, int Tfull, long F4, int t0, int len, int add, void* stream);
+int caddy_k_vgg_copy_f(const float* src, float* dst, long n, void* stream);
+int caddy_k_lpips_blocks(int npix);      /* partials per frame of a level with npix pixels */
+int caddy_k_lpips_stage(const float* src, float* out, int N, int H, int W, float range, void* stream);
+int caddy_k_lpips_head(const float* f0, int s0, const float* f1, int s1, const float* w, int nf, int npix, int C, int blocks, double* part /* [n * blocks + b] */, void* stream);
+int caddy_k_lpips_finalize(const double* part, const struct LpipsLevels* lv, long part_doubles, int nf, double* out /* (6, ldo) */, int ldo, void* stream);
 
 #ifdef __cplusplus
 }

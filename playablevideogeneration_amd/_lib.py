@@ -96,8 +96,16 @@ class VggLevels(C.Structure):
     _fields_ = [("numel", (C.c_double * 5) * 3)]
 
 
+class LpipsLevels(C.Structure):      # csrc/lpips.h: region of the partial slab, blocks per frame and 1 / (H_l W_l) of each level (caddy_k_lpips_finalize)
+    _fields_ = [("off", C.c_long * 5), ("blocks", C.c_int * 5), ("inv_px", C.c_double * 5)]
+
+
+class VggCosArgs(C.Structure):      # csrc/perceptual.h: the five tapped maps of both image batches (caddy_k_vgg_feat_cos)
+    _fields_ = [("x", _FP * 5), ("y", _FP * 5), ("x_s16", C.c_int * 5), ("y_s16", C.c_int * 5), ("H", C.c_int * 5), ("W", C.c_int * 5), ("C", C.c_int * 5)]
+
+
 ALLREDUCE_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_void_p)      # allreduce_hook_t(float* device_ptr, int count, void* user)
-HEAD_STRUCTS = (HeadParams, HeadBufs, SampleCfg, SmallLossArgs, DiagArgs, LossWeights, VggLevels, TV)      # index = the argument of caddy_k_struct_size
+HEAD_STRUCTS = (HeadParams, HeadBufs, SampleCfg, SmallLossArgs, DiagArgs, LossWeights, VggLevels, TV, LpipsLevels, VggCosArgs)      # index = the argument of caddy_k_struct_size
 
 
 def check_head_structs(lib):

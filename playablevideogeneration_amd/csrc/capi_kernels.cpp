@@ -5,6 +5,7 @@
 #include "pack.h"
 #include "head.h"
 #include "perceptual.h"
+#include "lpips.h"
 
 #define ST(s) ((hipStream_t)(s))
 extern "C" {
@@ -105,6 +106,8 @@ int caddy_k_struct_size(int which) {      // sizeof of the argument structs the 
         case 5: return (int)sizeof(LossWeights);
         case 6: return (int)sizeof(VggLevels);
         case 7: return (int)sizeof(TV);
+        case 8: return (int)sizeof(LpipsLevels);
+        case 9: return (int)sizeof(VggCosArgs);
         default: return -1;
     }
 }
@@ -125,4 +128,26 @@ int caddy_k_loss_finalize(double* acc, const LossWeights* w, double n0, double n
 int caddy_k_loss_diagnostics(const DiagArgs* d, const TV* states, const TV* hidden, void* s) { return loss_diagnostics(*d, *states, *hidden, ST(s)); }
 int caddy_k_loss_diff_per_frame(const TV* a, int Ta, int a_off, const TV* b, int Tb, int C, int sq, double* acc, void* s) { return loss_diff_per_frame(*a, Ta, a_off, *b, Tb, C, sq, acc, ST(s)); }
 int caddy_k_loss_report_flag(unsigned* flags, int n, double* slot, double* total, void* s) { return loss_report_flag(flags, n, slot, total, ST(s)); }
+// LPIPS head (lpips.hip) through its launchers; the point-wise kernels of perceptual.hip have their entry points (caddy_k_vgg_*) at the end of that file.  Arguments are validated
+// before anything is launched: -1 and no launch
+int caddy_k_lpips_blocks(int npix) { return npix < 1 ? -1 : lpips_blocks(npix); }
+int caddy_k_lpips_stage(const float* src, float* out, int N, int H, int W, float range, void* s) {      // (N, 3, H, W) -> (N, H, W, 4)
+    if (!src || !out || N < 1 || H < 1 || W < 1 || !(range > 0.f)) return -1;
+    lpips_stage_launch(ST(s), src, out, (long)N * H * W, (long)H * W, range);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// f0 / f1: dense maps of nf frames x npix pixels x C channels (fp32, or S16-f16 with s0 / s1), w: C weights, part: nf * blocks doubles.  C in {64, 128, 256, 512}, blocks in [1, 128]
+int caddy_k_lpips_head(const float* f0, int s0, const float* f1, int s1, const float* w, int nf, int npix, int C, int blocks, double* part, void* s) {
+    if (!f0 || !f1 || !w || !part || nf < 1 || nf > 65535 || npix < 1 || blocks < 1 || blocks > 128) return -1;
+    if (C != 64 && C != 128 && C != 256 && C != 512) return -1;
+    return lpips_head_launch(ST(s), f0, s0 != 0, f1, s1 != 0, w, nf, npix, C, blocks, part);
+}
+// part: the partial slab of part_doubles doubles; every level's region [off, off + nf * blocks) must lie inside it; out: (6, ldo) doubles, ldo >= nf
+int caddy_k_lpips_finalize(const double* part, const LpipsLevels* lv, long part_doubles, int nf, double* out, int ldo, void* s) {
+    if (!part || !lv || !out || nf < 1 || ldo < nf) return -1;
+    for (int l = 0; l < 5; l++)
+        if (lv->blocks[l] < 1 || lv->off[l] < 0 || lv->off[l] + (long)nf * lv->blocks[l] > part_doubles) return -1;
+    lpips_finalize_launch(ST(s), part, *lv, nf, out, ldo);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 }

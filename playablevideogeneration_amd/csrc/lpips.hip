@@ -66,6 +66,7 @@ __global__ __launch_bounds__(256) void k_lpips_head(const float* f0, const float
 
 // one thread per frame: the blocks of each level in order, / (H_l W_l); the levels in order
 __global__ __launch_bounds__(64) void k_lpips_finalize(const double* part, LpipsLevels lv, int nf, double* out, int ldo) {
+#pragma clang fp contract(off)      // the total is the sum of the level values AS STORED: no fused multiply-add of the last level's product onto it
     const int n = blockIdx.x * 64 + threadIdx.x;
     if (n >= nf) return;
     double total = 0.0;

@@ -16,6 +16,8 @@ struct VggState { bool enabled = false, loaded = false; int kind = VGG_KIND_VGG1
                   float* lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // LPIPS: the per-channel weights of lin{l}.model[1] (C_l floats each)
                   unsigned tap_s16 = 0; };                                             // LPIPS: bit l set = level l's taps travelled as S16 tensors in some chunk of the last caddy_frame_lpips
 struct VggLevels { double numel[3][5]; };      // elements of the level-l feature map at resolution r (N * C * H * W)
+// caddy_k_vgg_feat_cos (unit-parity tests): the five tapped maps of both image batches, dense NHWC of H[l] x W[l] x C[l] per frame, fp32 or (x_s16 / y_s16) S16-f16
+struct VggCosArgs { const float* x[5]; const float* y[5]; int x_s16[5]; int y_s16[5]; int H[5]; int W[5]; int C[5]; };
 
 struct caddy_ctx;
 struct caddy_param_info;

@@ -772,3 +772,91 @@ int vgg_lpips_chunk(caddy_ctx* c, const float* ref, const float* gen, int nf, fl
     }
     return c->fail ? -1 : 0;
 }
+
+// ---- per-kernel entry points (unit-parity tests; include/caddy_hip.h) ----
+// Each launches one point-wise kernel of this file on caller-supplied device buffers through the drivers' own dispatch (launch_* / grid_for / cos_blocks above: the same flag-to-
+// instance mapping, no kernel instance of its own).  Maps are dense NHWC (pitch == C).  Arguments are validated BEFORE anything is launched: -1 and no launch for a null pointer,
+// a non-positive size, C % 4 != 0, an S16 operand with C % 32 != 0, and what each entry point names below.
+namespace {
+bool kmap_ok(const void* p, int N, int H, int W, int C, int s16) { return p && N >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0 && N <= 65535 && (!s16 || C % 32 == 0); }
+T4 kmap(const float* d, float* g, int N, int H, int W, int C, int s16) {
+    T4 t{};
+    t.d = const_cast<float*>(d); t.g = g; t.N = N; t.H = H; t.W = W; t.C = C; t.sn = (long)H * W * C; t.ld = C; t.fmt = s16 ? 1 : 0;
+    return t;
+}
+int klaunched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+}  // namespace
+
+int caddy_k_vgg_maxpool2(const float* in, float* out, int N, int H, int W, int C, void* stream) {      // fp32 only, as vgg_forward launches it
+    if (!kmap_ok(in, N, H, W, C, 0) || !out) return -1;
+    const long n4 = (long)N * (H / 2) * (W / 2) * (C / 4);
+    hipLaunchKernelGGL(k_maxpool2, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream, in, out, n4, H, W, C / 4);
+    return klaunched();
+}
+int caddy_k_vgg_maxpool2_bwd_relu(const float* a, int a_s16, const float* gp, float* gz, int gz_s16, int N, int H, int W, int C, void* stream) {
+    if (!kmap_ok(a, N, H, W, C, a_s16 || gz_s16) || !gp || !gz) return -1;
+    launch_maxpool_bwd((hipStream_t)stream, kmap(a, gz, N, H, W, C, a_s16), gp, gz_s16 != 0);
+    return klaunched();
+}
+int caddy_k_vgg_feat_l1(const float* rec, int rec_s16, const float* gt, int gt_s16, int N, int H, int W, int C, float seed_w, float* gz, int gz_s16, double* acc, void* stream) {
+    if (!kmap_ok(rec, N, H, W, C, rec_s16 || gt_s16 || (gz && gz_s16)) || !gt || !acc) return -1;
+    launch_feat_l1((hipStream_t)stream, kmap(rec, nullptr, N, H, W, C, rec_s16), kmap(gt, nullptr, N, H, W, C, gt_s16), seed_w, gz, gz_s16 != 0, acc);
+    return klaunched();
+}
+int caddy_k_vgg_feat_l1_img(const float* rec, int rec_s16, const float* gt, int gt_s16, int N, int H, int W, int C, double* acc, void* stream) {
+    if (!kmap_ok(rec, N, H, W, C, rec_s16 || gt_s16) || !gt || !acc) return -1;
+    launch_feat_l1_img((hipStream_t)stream, kmap(rec, nullptr, N, H, W, C, rec_s16), kmap(gt, nullptr, N, H, W, C, gt_s16), acc);
+    return klaunched();
+}
+int caddy_k_vgg_cos_blocks(int H, int W, int C) {      // workgroups (= partial triples) per image of the per-image kernels on an H x W x C map
+    if (H < 1 || W < 1 || C < 4 || C % 4) return -1;
+    return cos_blocks(kmap(nullptr, nullptr, 1, H, W, C, 0));
+}
+// the cosine path of vgg_metric_chunk on the caller's five levels: part = the partial slab (part_doubles >= sum_l 3 * nf * cos_blocks_l doubles, level regions in order), out = nf
+// doubles.  -1 if the slab is too small
+int caddy_k_vgg_feat_cos(const VggCosArgs* a, int nf, double* part, long part_doubles, double* out, void* stream) {
+    if (!a || !part || !out || nf < 1) return -1;
+    T4 tx[5], ty[5];
+    CosLevels lv{};
+    long total = 0;
+    for (int l = 0; l < 5; l++) {
+        if (!kmap_ok(a->x[l], nf, a->H[l], a->W[l], a->C[l], a->x_s16[l] || a->y_s16[l]) || !a->y[l]) return -1;
+        tx[l] = kmap(a->x[l], nullptr, nf, a->H[l], a->W[l], a->C[l], a->x_s16[l]);
+        ty[l] = kmap(a->y[l], nullptr, nf, a->H[l], a->W[l], a->C[l], a->y_s16[l]);
+        lv.off[l] = total; lv.blocks[l] = cos_blocks(tx[l]); total += (long)nf * lv.blocks[l] * 3;
+    }
+    if (total > part_doubles) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    for (int l = 0; l < 5; l++) launch_feat_cos_img(st, tx[l], ty[l], part + lv.off[l]);
+    hipLaunchKernelGGL(k_feat_cos_finalize, dim3((nf + 63) / 64), dim3(64), 0, st, (const double*)part, lv, nf, out);
+    return klaunched();
+}
+int caddy_k_vgg_metric_stage(const float* src, float* out, int N, int H, int W, float range, void* stream) {      // (N, 3, H, W) -> (N, H, W, 4)
+    if (!src || !out || N < 1 || H < 1 || W < 1 || !(range > 0.f)) return -1;
+    const long npix = (long)N * H * W;
+    hipLaunchKernelGGL(k_metric_stage, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, src, out, npix, (long)H * W, range);
+    return klaunched();
+}
+// obs: B * Tobs frames of f Ho x f Wo pixels, pitch ld >= 3; out: (B * Trec, Ho, Wo, 4).  -1 for f outside {1, 2, 4}, an observation that is not f times the output, or a time
+// window [t_off, t_off + Trec) that leaves the sequence
+int caddy_k_vgg_gt_resize(const TV* obs, float* out, int Ho, int Wo, int B, int Tobs, int Trec, int t_off, int f, void* stream) {
+    if (!obs || !obs->p || !out || Ho < 1 || Wo < 1 || B < 1 || Tobs < 1 || Trec < 1 || t_off < 0) return -1;
+    if (f != 1 && f != 2 && f != 4) return -1;
+    if (obs->H % f || obs->W % f || obs->H != f * Ho || obs->W != f * Wo || obs->ld < 3 || obs->sn < (long)obs->H * obs->W * obs->ld) return -1;
+    if (t_off + Trec > Tobs || obs->N != B * Tobs) return -1;
+    const long npix = (long)B * Trec * Ho * Wo;
+    hipLaunchKernelGGL(k_gt_resize, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, *obs, out, Ho, Wo, npix, f, t_off, Tobs, Trec);
+    return klaunched();
+}
+// full: (B, Tfull) frames of F4 float4, chunk: (B, len) frames; add = 0 gathers the time steps [t0, t0 + len) into chunk, add = 1 adds chunk onto them.  -1 unless 0 <= t0 and t0 + len <= Tfull
+int caddy_k_vgg_time_chunk(float* full, float* chunk, int B, int Tfull, long F4, int t0, int len, int add, void* stream) {
+    if (!full || !chunk || B < 1 || Tfull < 1 || F4 < 1 || t0 < 0 || len < 1 || t0 + len > Tfull) return -1;
+    const long total4 = (long)B * len * F4;
+    hipLaunchKernelGGL(k_time_chunk, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, (float4*)full, (float4*)chunk, F4, Tfull, t0, len, total4, add ? 1 : 0);
+    return klaunched();
+}
+int caddy_k_vgg_copy_f(const float* src, float* dst, long n, void* stream) {      // one workgroup, as vgg_load launches it
+    if (!src || !dst || n < 0) return -1;
+    hipLaunchKernelGGL(k_copy_f, dim3(1), dim3(256), 0, (hipStream_t)stream, src, dst, n);
+    return klaunched();
+}
