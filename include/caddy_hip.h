@@ -423,6 +423,62 @@ caddy_ctx* caddy_png_read_ctx_create(int max_frames, int H, int W, void* workspa
  * files[0, offsets[n]).  One launch per chunk of max_frames images on the context's stream; waits for nothing, allocates nothing.  Returns 0 when it
  * ran -- the verdicts are in status.  Errors (-2, caddy_last_error; nothing is launched): a context of another kind, null pointers, misaligned offsets or status, n < 1. */
 int caddy_png_decode(caddy_ctx* ctx, const unsigned char* files, const unsigned* offsets, int n, unsigned char* frames_u8, int* status);     /* dataset/video.py:136-157 */
+/* --- Device-side JPEG reader (csrc/jpeg_read.hip): the files of a frame folder whose frames are .jpg (dataset/video.py:120-126 discovers the extension, Image.open reads
+ *     anything) and the frames of the MJPEG files caddy_video_encode writes, parsed, Huffman-decoded, inverse-transformed, upsampled and colour-converted on the device.  A
+ *     JPEG-read context is an evaluation context of its own kind (no model, no weights) for images of H x W, each 1..4096; a call with more than max_frames images runs in
+ *     chunks.  Destroy with caddy_ctx_destroy.
+ *     Accepted: SOI; baseline sequential DCT (SOF0), precision 8, three components, chroma 1x1 and luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0), width and height those of the
+ *     context; one interleaved scan of the three components in frame order with Ss = 0, Se = 63, Ah = Al = 0; Huffman tables 0..3 per class and 8-bit DQT tables 0..3, any
+ *     number of DQT / DHT segments of one or several tables each, redefined at will before SOS (the last definition holds); DRI, 0 included; APPn and COM skipped; 0xFF fill
+ *     bytes in front of a marker; bytes behind EOI ignored.  Colour space by libjpeg's rule: a JFIF APP0 means YCbCr; else an Adobe APP14 with transform 1 means YCbCr and with
+ *     0 or 2 is refused; with neither, the component ids 'R','G','B' are refused and any other ids mean YCbCr.
+ *     Contract: for every accepted file an encoder wrote, frames_u8 is byte for byte what Pillow (libjpeg-turbo) decodes: Image.open(..).convert("RGB").  For handwritten or
+ *     mutated streams the arbiter is the arithmetic below (libjpeg's own result there depends on its build: long arithmetic with a range-limit table in C, saturating 16 / 32-bit
+ *     lanes in SIMD).  All of it is integer, >> is arithmetic, products and sums are formed on 32-bit two's-complement words (computed on unsigned, so nothing is undefined):
+ *       entropy   T.81 F.2.2.  EXTEND(v, s) = v < 2^(s-1) ? v - 2^s + 1 : v.  The DC predictor of every component is 0 at the start of the scan and of every restart interval.
+ *                 An AC symbol (r, s): s = 0 and r = 15 is ZRL (16 zeros), s = 0 and any other r ends the block (EOB, as libjpeg reads it); no EOB is needed once index 63 is
+ *                 written.  In the scan 0xFF, any further 0xFF, 0x00 is one 0xFF data byte; 0xFF, any further 0xFF, then a byte other than 0x00 is a marker, and the interval
+ *                 ends in front of the first of those 0xFF.
+ *       restarts  with Ri > 0 the scan is ceil(MCUs / Ri) intervals, between them exactly RSTm with m = k mod 8 for the k-th; every interval is decoded on its own, and its
+ *                 bytes must be used up by its MCUs to within the < 8 padding bits (whose value is not checked)
+ *       dequant   c[zigzag[k]] = value * table[k]
+ *       IDCT      libjpeg's jidctint.c (CONST_BITS 13, PASS1_BITS 2, its twelve FIX_* constants): columns first with DESCALE(., 11), then rows with DESCALE(., 18), + 128,
+ *                 clamped to 0..255; DESCALE(x, n) = (x + (1 << (n-1))) >> n
+ *       chroma    a plane has the true size cw = ceil(W hs / hmax), ch = ceil(H vs / vmax); samples outside it are never read, neighbours are replicated at its edge.
+ *                 h2v1 fancy: out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2, first = s[0], last = s[cw-1].
+ *                 h2v2 fancy: v[i] = 3 s[r][i] + s[r'][i], r' the row above for an even output row and the row below for an odd one (row -1 := row 0, row ch := row ch-1);
+ *                 out[2i] = (3 v[i] + v[i-1] + 8) >> 4, out[2i+1] = (3 v[i] + v[i+1] + 7) >> 4, first column (4 v[0] + 8) >> 4, last (4 v[cw-1] + 7) >> 4
+ *       colour    (jdcolor.c) cb, cr = sample - 128; R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ *                 each clamped to 0..255
+ *     Deliberately stricter than libjpeg, which warns and carries on: see the statuses.  The first cause met decides: the markers in file order up to SOS, then the markers of
+ *     the scan (count, order, the one behind the scan), then the intervals in order.
+ *     Safety: every read of the blob is bounded by the end of that file (clamped to offsets[n]) and every read of a lane by the end of its interval; past it the bit reader
+ *     yields zeros and the first symbol that used one ends the image; every write is bounded by the image's own frame and workspace slice; a bad file costs its own status
+ *     word, its frame is zero-filled and the other images decode normally. --- */
+#define CADDY_JPEG_OK 0
+#define CADDY_JPEG_NOT_JPEG 1          /* no SOI */
+#define CADDY_JPEG_TRUNCATED 2         /* the file ends inside a segment, before SOS, or inside the scan: before its last MCU is decoded or with no marker behind the scan */
+#define CADDY_JPEG_UNSUPPORTED 3       /* SOF1/2/3/5..15, DAC, DHP, EXP; precision other than 8; 1 or 4 components; other sampling; a scan of fewer components or in another order
+                                          (non-interleaved, multiple scans); 16-bit DQT; DNL or height 0; the colour cases above; scan parameters other than 0 / 63 / 0 / 0 */
+#define CADDY_JPEG_GEOMETRY 4          /* width or height other than the context's */
+#define CADDY_JPEG_BAD_TABLE 5         /* a segment length inconsistent with its content; a byte other than 0xFF where a marker must stand, or SOI / RSTm / TEM / 0xFF 0x00
+                                          before SOS; a DQT / DHT / component table id out of range; a referenced table never defined; Huffman counts that over-subscribe the
+                                          code space or pass 256 symbols; a second SOF; no SOF before SOS */
+#define CADDY_JPEG_BAD_CODE 6          /* a bit pattern that is no code of the table */
+#define CADDY_JPEG_BAD_COEFFICIENT 7   /* a DC category above 11; an AC size above 10; a run (ZRL included) that passes index 63; a DC value outside -2048..2047 */
+#define CADDY_JPEG_BAD_RESTART 8       /* the number of RSTm markers is not ceil(MCUs / Ri) - 1; they are out of the cyclic order; an interval in front of an RSTm needs more bits
+                                          than it has, or leaves whole bytes over */
+#define CADDY_JPEG_BAD_SCAN 9          /* whole entropy bytes are left over behind the last MCU; a marker other than EOI follows the scan */
+/* 0 (caddy_last_error): max_frames outside 1..65535, H or W outside 1..4096 */
+size_t caddy_jpeg_read_workspace_bytes(int max_frames, int H, int W);
+caddy_ctx* caddy_jpeg_read_ctx_create(int max_frames, int H, int W, void* workspace, size_t bytes);
+/* files (device): n files back to back; offsets (device, n + 1 words, 4-byte aligned): where each starts and, last, the total length -- what caddy_video_encode leaves, so its
+ * output decodes without touching the host.  frames_u8 (device, (n, H, W, 3) uint8, any alignment) and status (device, n words, 4-byte aligned, CADDY_JPEG_*) receive the
+ * result.  Offsets that are not monotonic or pass offsets[n] give that image an empty or shortened file, never a read outside files[0, offsets[n]).  Three launches per chunk
+ * of max_frames images on the context's stream: entropy decoding (one wave per image, one lane per restart interval), IDCT (block-parallel), upsampling
+ * and colour (pixel-parallel).  Waits for nothing, allocates nothing.  Returns 0 when it ran -- the verdicts are in status.  Errors (-2, caddy_last_error; nothing is launched):
+ * a context of another kind, null pointers, misaligned offsets or status, n < 1. */
+int caddy_jpeg_decode(caddy_ctx* ctx, const unsigned char* files, const unsigned* offsets, int n, unsigned char* frames_u8, int* status);    /* dataset/video.py:120-157 */
 /* on (default): caddy_start_inference folds every eval-mode BatchNorm of the roll-out path (E, R's non-recurrent blocks, D) into the packed
  * weights / bias of the convolution in front of it, and caddy_generate_next runs the folded graph (LeakyReLU and the residual add in the conv
  * epilogues, the ConvLSTM cells' BatchNorm as a second output of the gate kernel): ~35 fewer launches per frame.  off: one BatchNorm launch per

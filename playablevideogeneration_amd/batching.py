@@ -179,23 +179,24 @@ def raw_batch_elements_collate_fn(batch: List[RawBatchElement]) -> RawBatch:
 
 
 class CodedBatchElement(RawBatchElement):
-    """A RawBatchElement whose `frames` are still files (video_dataset.raw_frame_spec(decode="device")): uint8 arrays of the bytes of each distinct frame's PNG,
-    all of `frame_hw` = (h, w); `sources[k]` = (video path, frame index) of frame k, for messages."""
+    """A RawBatchElement whose `frames` are still files (video_dataset.raw_frame_spec(decode="device")): uint8 arrays of the bytes of each distinct frame's PNG -- or,
+    with `codec` "jpeg", JPEG -- file, all of `frame_hw` = (h, w); `sources[k]` = (video path, frame index) of frame k, for messages."""
 
-    def __init__(self, frames, frame_hw, sources, stack_indices, actions, rewards, dones, spec, video=None, initial_frame_index: int = 0):
+    def __init__(self, frames, frame_hw, sources, stack_indices, actions, rewards, dones, spec, video=None, initial_frame_index: int = 0, codec: str = "png"):
         super().__init__(frames, stack_indices, actions, rewards, dones, spec, video, initial_frame_index)
-        self.frame_hw, self.sources = tuple(frame_hw), list(sources)
+        self.frame_hw, self.sources, self.codec = tuple(frame_hw), list(sources), codec
 
 
 class CodedBatch(RawBatch):
     """A RawBatch before its frames are decoded: `blob` uint8, the PNG files of the distinct frames back to back, `offsets` int32 (F + 1), `frame_hw` their common
     (h, w).  `decode()` gives the RawBatch with `frames` on the device (png_reader.PngDecoder: the compressed bytes cross the bus, the device inflates and unfilters);
-    `observations()` / `to_tuple()` decode first and return what RawBatch returns, bit for bit.  A file the decoder refuses raises, naming its video and frame."""
+    `observations()` / `to_tuple()` decode first and return what RawBatch returns, bit for bit.  A file the decoder refuses raises, naming its video and frame.
+    `codec` "jpeg": the files are JPEG and jpeg_reader.JpegDecoder decodes them (Huffman decoding, IDCT, upsampling and colour on the device)."""
 
     def __init__(self, blob: torch.Tensor, offsets: torch.Tensor, frame_hw, sources, slot_src: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor, dones: torch.Tensor, spec,
-                 videos=None, initial_frames=None):
+                 videos=None, initial_frames=None, codec: str = "png"):
         super().__init__(None, slot_src, actions, rewards, dones, spec, videos, initial_frames)
-        self.blob, self.offsets, self.sources = blob, offsets, list(sources)
+        self.blob, self.offsets, self.sources, self.codec = blob, offsets, list(sources), codec
         self._hw = (int(frame_hw[0]), int(frame_hw[1]))
 
     @property
@@ -211,10 +212,13 @@ class CodedBatch(RawBatch):
 
     def device_frames(self, staged: Tuple, lib=None, device=None) -> torch.Tensor:
         from . import metrics as M
-        from .png_reader import cached_png_decoder, status_error
+        if self.codec == "jpeg":
+            from .jpeg_reader import cached_jpeg_decoder as cached_decoder, status_error
+        else:
+            from .png_reader import cached_png_decoder as cached_decoder, status_error
         device = torch.device(device) if device is not None else M.device(lib)
         blob, offsets = (t.to(device, non_blocking=True) for t in staged)
-        frames, status = cached_png_decoder(self._hw[0], self._hw[1], self.n_frames, lib, device).decode_stream(blob, offsets)
+        frames, status = cached_decoder(self._hw[0], self._hw[1], self.n_frames, lib, device).decode_stream(blob, offsets)
         error = status_error(status.cpu().tolist(), [f"{path} frame {index}" for path, index in self.sources])
         if error is not None:
             raise error
@@ -233,9 +237,11 @@ class CodedBatch(RawBatch):
 def coded_batch_elements_collate_fn(batch: List[CodedBatchElement]) -> CodedBatch:
     """the collate function of CodedBatchElements: the files are concatenated once each, the stack indices shifted by the frames in front of their element"""
     import numpy as np
-    hw = batch[0].frame_hw
+    hw, codec = batch[0].frame_hw, batch[0].codec
     files, sources, slots = [], [], []
     for el in batch:
+        if el.codec != codec:
+            raise Exception(f"frames of different codecs in one batch: {codec} and {el.codec} ({el.sources[0][0]}; such datasets keep the host decoder)")
         if el.frame_hw != hw:
             raise Exception(f"frames of different sizes in one batch: {hw} and {el.frame_hw} ({el.sources[0][0]}; such datasets keep the host transform)")
         slots.append(torch.tensor(el.stack_indices, dtype=torch.int32) + len(files))
@@ -249,7 +255,7 @@ def coded_batch_elements_collate_fn(batch: List[CodedBatchElement]) -> CodedBatc
     rewards = torch.stack([torch.tensor(el.rewards) for el in batch], dim=0)
     dones = torch.stack([torch.tensor(el.dones) for el in batch], dim=0)
     return CodedBatch(torch.from_numpy(np.concatenate(files)), torch.from_numpy(offsets.astype(np.int32)), hw, sources, torch.stack(slots, dim=0), actions, rewards, dones,
-                      batch[0].spec, [el.video for el in batch], [el.initial_frame_index for el in batch])
+                      batch[0].spec, [el.video for el in batch], [el.initial_frame_index for el in batch], codec)
 
 
 def collate_fn_for(element):

@@ -8,7 +8,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["conv_mfma.hip", "conv_hx.hip", "conv_hx_co.hip", "conv_hx_wgrad.hip", "conv_head.hip", "conv_direct.hip", "conv_thin.hip", "conv_narrow.hip", "conv_stream.hip", "pointwise.hip", "pack.hip", "head.hip", "perceptual.hip", "frame_metrics.hip", "lpips.hip", "fid.hip", "fvd.hip", "detection.hip", "frames.hip", "sheets.hip", "video.hip", "png.hip", "png_read.hip", "net.cpp", "eval_ctx.cpp", "capi_kernels.cpp", "dp_rccl.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_hx.hip", "conv_hx_co.hip", "conv_hx_wgrad.hip", "conv_head.hip", "conv_direct.hip", "conv_thin.hip", "conv_narrow.hip", "conv_stream.hip", "pointwise.hip", "pack.hip", "head.hip", "perceptual.hip", "frame_metrics.hip", "lpips.hip", "fid.hip", "fvd.hip", "detection.hip", "frames.hip", "sheets.hip", "video.hip", "png.hip", "png_read.hip", "jpeg_read.hip", "net.cpp", "eval_ctx.cpp", "capi_kernels.cpp", "dp_rccl.cpp"]
 LIB = os.path.join(HERE, "libcaddy_hip.so")
 
 

@@ -18,7 +18,7 @@ bool ctx_needs(caddy_ctx* c, int kinds, const char* who) {
         return false;
     }
     if (c && (c->kind & kinds)) return true;
-    set_error(std::string(who) + " needs a context from " + (kinds & CTX_METRICS ? "caddy_metrics_ctx_create" : kinds & CTX_LPIPS ? "caddy_lpips_ctx_create" : kinds & CTX_FID ? "caddy_fid_ctx_create" : kinds & CTX_IS ? "caddy_is_ctx_create" : kinds & CTX_FRAMES ? "caddy_frames_ctx_create" : kinds & CTX_SHEETS ? "caddy_sheets_ctx_create" : kinds & CTX_VIDEO ? "caddy_video_ctx_create" : kinds & CTX_PNG ? "caddy_png_ctx_create" : kinds & CTX_PNG_READ ? "caddy_png_read_ctx_create" : "caddy_fvd_ctx_create"));
+    set_error(std::string(who) + " needs a context from " + (kinds & CTX_METRICS ? "caddy_metrics_ctx_create" : kinds & CTX_LPIPS ? "caddy_lpips_ctx_create" : kinds & CTX_FID ? "caddy_fid_ctx_create" : kinds & CTX_IS ? "caddy_is_ctx_create" : kinds & CTX_FRAMES ? "caddy_frames_ctx_create" : kinds & CTX_SHEETS ? "caddy_sheets_ctx_create" : kinds & CTX_VIDEO ? "caddy_video_ctx_create" : kinds & CTX_PNG ? "caddy_png_ctx_create" : kinds & CTX_PNG_READ ? "caddy_png_read_ctx_create" : kinds & CTX_JPEG_READ ? "caddy_jpeg_read_ctx_create" : "caddy_fvd_ctx_create"));
     return false;
 }
 

@@ -11,6 +11,7 @@
 #include "video.h"
 #include "png.h"
 #include "png_read.h"
+#include "jpeg_read.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1684,6 +1685,7 @@ void caddy_ctx_destroy(caddy_ctx* c) {
     video_free(c);
     png_free(c);
     png_read_free(c);
+    jpeg_read_free(c);
     delete c;
 }
 int caddy_set_stream(caddy_ctx* c, void* s) { c->stream = (hipStream_t)s; return 0; }

@@ -74,7 +74,8 @@ enum { CTX_MODEL = 1,       // caddy_ctx_create
        CTX_SHEETS = 128,    // caddy_sheets_ctx_create (sheets.hip: evaluation example sheets; no model, no weights)
        CTX_VIDEO = 256,     // caddy_video_ctx_create (video.hip: baseline JPEG encoder of the MJPEG video writer; no model, no weights)
        CTX_PNG = 512,       // caddy_png_ctx_create (png.hip: PNG filter + deflate of the PNG writer; no model, no weights)
-       CTX_PNG_READ = 1024 };      // caddy_png_read_ctx_create (png_read.hip: PNG parse + inflate + unfilter of the PNG reader; no model, no weights)
+       CTX_PNG_READ = 1024,        // caddy_png_read_ctx_create (png_read.hip: PNG parse + inflate + unfilter of the PNG reader; no model, no weights)
+       CTX_JPEG_READ = 2048 };     // caddy_jpeg_read_ctx_create (jpeg_read.hip: JPEG parse + Huffman decode + IDCT + upsample of the JPEG reader; no model, no weights)
 
 struct BNL;
 #define CADDY_N_FLAGS 128
@@ -269,6 +270,7 @@ struct caddy_ctx {
     struct VideoState* vid = nullptr;       // MJPEG video writer (caddy_video_ctx_create; video.hip owns it)
     struct PngState* png = nullptr;         // PNG writer (caddy_png_ctx_create; png.hip owns it)
     struct PngReadState* png_read = nullptr;      // PNG reader (caddy_png_read_ctx_create; png_read.hip owns it)
+    struct JpegReadState* jpeg_read = nullptr;    // JPEG reader (caddy_jpeg_read_ctx_create; jpeg_read.hip owns it)
 
     // ---- optional per-launch timing of the conv kernels (HIP events on the launch stream; bench.py roofline) ----
     struct ProfRec { hipEvent_t a, b; int fam; double flops; int P, K, Cout, KS, kind; double bytes; };   // kind: 0 fwd, 1 dgrad (accumulate), 2 wgrad

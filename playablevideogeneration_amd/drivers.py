@@ -414,9 +414,10 @@ def evaluate_loop(config, logger) -> Dict:
     from .video_dataset import VideoDataset, evaluation_transform, raw_frame_spec
     size = config["data"]["target_input_size"]
     logger.print("- Loading datasets")
-    decode = "device" if config["evaluation"].get("device_decode", False) else "host"      # opt-in: the PNG files decoded on the GPU too (png_reader.py); implies device_transforms
+    jpeg = bool(config["evaluation"].get("device_decode_jpeg", False))      # opt-in: .jpg frame folders decoded on the GPU as well (jpeg_reader.py); implies device_decode
+    decode = "device" if jpeg or config["evaluation"].get("device_decode", False) else "host"      # opt-in: the PNG files decoded on the GPU too (png_reader.py); implies device_transforms
     if decode == "device" or config["evaluation"].get("device_transforms", False):      # opt-in: crop, resize and x / 255 on the GPU (frame_pipeline.py)
-        def transform(crop): return raw_frame_spec(crop, size, 1, decode)
+        def transform(crop): return raw_frame_spec(crop, size, 1, decode, ("png", "jpeg") if jpeg else ("png",))
     else:
         def transform(crop): return evaluation_transform(crop, size)
     reference = VideoDataset(config["reference_data"]["data_root"], config["evaluation"]["batching"], transform(config["reference_data"].get("crop")))

@@ -59,8 +59,9 @@ class ModelRollouts:
         self.config, self.model, self.logger = config, model, logger
         size = config["model"]["representation_network"]["target_input_size"]
         self.dataset = copy.copy(dataset)      # the same videos and sample grid, undecorated frames
-        self.device_decode = bool(config["data"].get("device_decode", False))      # opt-in: the workers ship the PNG files, the device decodes them (png_reader.py)
-        self.dataset.final_transform = raw_frame_spec(config["data"].get("crop"), size, 0, "device" if self.device_decode else "host")
+        jpeg = bool(config["data"].get("device_decode_jpeg", False))      # opt-in: .jpg frame folders too (jpeg_reader.py); implies device_decode
+        self.device_decode = jpeg or bool(config["data"].get("device_decode", False))      # opt-in: the workers ship the PNG files, the device decodes them (png_reader.py)
+        self.dataset.final_transform = raw_frame_spec(config["data"].get("crop"), size, 0, "device" if self.device_decode else "host", ("png", "jpeg") if jpeg else ("png",))
         self.ground_truth_observations_init = config["evaluation_dataset"]["ground_truth_observations_init"]
         self.temperature = config["training"]["gumbel_temperature_end"]
         b = config["evaluation"]["batching"]

@@ -9,7 +9,7 @@ pipeline (frame_pipeline.FramePipeline) reads them.
     decode_pngs         the frames, or ValueError naming the first file that failed
     probe               (width, height, bit depth, colour type, interlace) from the first 29 bytes on the host: what a caller needs to pick the context, no decoding
 
-Not built: palette / grey / 16-bit / alpha images, interlacing, JPEG frames, a parallel split of one stream (inflate is one lane per image).  There is no host fallback: the
+Not built: palette / grey / 16-bit / alpha images, interlacing, a parallel split of one stream (inflate is one lane per image).  There is no host fallback: the
 kernels of the library in use (libcaddy_hip.so, or the tests' host simulator) are the only decoder.
 """
 import ctypes as C

@@ -123,21 +123,24 @@ def evaluation_transform(crop, target_input_size) -> Callable:
 class RawFrameSpec:
     """Marker a VideoDataset takes in place of a transform: its frames leave the dataset undecorated and `crop` ([left, upper, right, lower] or None), the resize to
     `size` ((width, height)) and the normalisation of `mode` (0: final_transform's [-1, 1], 1: evaluation_transform's [0, 1]) run on the device.  `decode`: "host"
-    (the workers decode with PIL and ship uint8 frames) or "device" (they ship the PNG files' bytes, png_reader.py decodes them on the device)."""
+    (the workers decode with PIL and ship uint8 frames) or "device" (they ship the PNG files' bytes, png_reader.py decodes them on the device).  `codecs`: what
+    decode="device" lets through, ("png",) or ("png", "jpeg"); with "jpeg" the folders whose frames are .jpg / .jpeg ship those files and jpeg_reader.py decodes them."""
 
-    def __init__(self, crop, size, mode: int, decode: str = "host"):
+    def __init__(self, crop, size, mode: int, decode: str = "host", codecs=("png",)):
         if mode not in (0, 1):
             raise ValueError(f"mode must be 0 ([-1, 1]) or 1 ([0, 1]), got {mode}")
         if decode not in ("host", "device"):
             raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
-        self.decode = decode
+        if tuple(codecs) not in (("png",), ("png", "jpeg")):
+            raise ValueError(f"codecs must be ('png',) or ('png', 'jpeg'), got {codecs!r}")
+        self.decode, self.codecs = decode, tuple(codecs)
         self.crop = None if crop is None else tuple(int(v) for v in crop)
         self.size = tuple(int(v) for v in size)
         self.mode = int(mode)
 
 
-def raw_frame_spec(crop, size, mode: int, decode: str = "host") -> RawFrameSpec:
-    return RawFrameSpec(crop, size, mode, decode)
+def raw_frame_spec(crop, size, mode: int, decode: str = "host", codecs=("png",)) -> RawFrameSpec:
+    return RawFrameSpec(crop, size, mode, decode, codecs)
 
 
 class VideoDataset(Dataset):
@@ -214,6 +217,8 @@ class VideoDataset(Dataset):
     def _coded_element(self, video, first, obs_idx, stacks, order, where) -> CodedBatchElement:
         """the sample's distinct frames as the bytes of their files; only what the device decoder reads is let through: PNG, 8-bit RGB, not interlaced, one size"""
         from .png_reader import probe
+        if video.extension.lower() in ("jpg", "jpeg") and "jpeg" in self.final_transform.codecs:
+            return self._coded_jpeg_element(video, first, obs_idx, stacks, order, where)
         if video.extension.lower() != "png":
             raise Exception(f"{video.frame_path(order[0])}: the device decoder reads PNG files only (such datasets keep the host decoder)")
         files, hw = [], None
@@ -232,6 +237,28 @@ class VideoDataset(Dataset):
             files.append(np.frombuffer(data, np.uint8))
         return CodedBatchElement(files, hw, [(video.frames_path, i) for i in order], [[where[i] for i in st] for st in stacks], [video.actions[i] for i in obs_idx],
                                  accumulated_rewards(video.rewards, obs_idx, self.skip_frames), [video.dones[i] for i in obs_idx], self.final_transform, video, first)
+
+
+    def _coded_jpeg_element(self, video, first, obs_idx, stacks, order, where) -> CodedBatchElement:
+        """the same for a folder of .jpg frames; only what the device decoder reads is let through: baseline, 8-bit, three components, 4:4:4 / 4:2:2 / 4:2:0, one size"""
+        from .jpeg_reader import probe, unsupported
+        files, hw = [], None
+        for i in order:
+            data = video.read_frame_bytes(i)
+            try:
+                info = probe(data)
+            except ValueError as e:
+                raise Exception(f"{video.frame_path(i)}: {e}")
+            why = unsupported(info)
+            if why is not None:
+                raise Exception(f"{video.frame_path(i)}: {why}; the device decoder does not read it (such datasets keep the host decoder)")
+            width, height = info[:2]
+            if hw is not None and (height, width) != hw:
+                raise Exception(f"{video.frame_path(i)}: {width} x {height}, the frames before it {hw[1]} x {hw[0]}: frames of different sizes in one batch")
+            hw = (height, width)
+            files.append(np.frombuffer(data, np.uint8))
+        return CodedBatchElement(files, hw, [(video.frames_path, i) for i in order], [[where[i] for i in st] for st in stacks], [video.actions[i] for i in obs_idx],
+                                 accumulated_rewards(video.rewards, obs_idx, self.skip_frames), [video.dones[i] for i in obs_idx], self.final_transform, video, first, "jpeg")
 
 
 def generate_splits(config) -> Dict[str, Tuple[str, Dict, Optional[List[str]]]]:
@@ -254,9 +281,10 @@ def generate_splits(config) -> Dict[str, Tuple[str, Dict, Optional[List[str]]]]:
 
 def build_datasets(config) -> Dict[str, VideoDataset]:
     """what train.py:42-51 does before it calls the trainer / evaluator factories"""
-    decode = "device" if config["data"].get("device_decode", False) else "host"      # opt-in: the workers ship the files, the GPU decodes them (implies device_transforms)
+    jpeg = bool(config["data"].get("device_decode_jpeg", False))      # opt-in: .jpg frame folders decode on the GPU too (jpeg_reader.py); implies device_decode
+    decode = "device" if jpeg or config["data"].get("device_decode", False) else "host"      # opt-in: the workers ship the files, the GPU decodes them (implies device_transforms)
     if decode == "device" or config["data"].get("device_transforms", False):      # opt-in: the workers decode, the GPU crops, resizes, normalises and stacks
-        tf = raw_frame_spec(config["data"]["crop"], config["model"]["representation_network"]["target_input_size"], 0, decode)
+        tf = raw_frame_spec(config["data"]["crop"], config["model"]["representation_network"]["target_input_size"], 0, decode, ("png", "jpeg") if jpeg else ("png",))
     else:
         tf = final_transform(config)
     return {k: VideoDataset(path, batching, tf, allowed) for k, (path, batching, allowed) in generate_splits(config).items()}
